@@ -1,24 +1,31 @@
 """Benchmark of the MCAQ spatial-adaptive-quantization hook path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--pipeline D]
-                    [--no-cpu] [--no-e2e] [--e2e [--amp]] [--eager]
+                    [--full [--no-cpu] [--no-e2e]] [--dump-outputs DIR] [--e2e [--amp]] [--eager]
 
 The headline (`metric`, `value`) is the HOOK PATH: a step = the three
 backbone hooks (C3/C4/C5) of one batch - channel statistics, morphological
 complexity (phi1..5, MLP, bilateral), bit mapper, soft mask and the tile-wise
 2..8-bit quant/dequant, every output the reference hook produces - computed
-by the HIP kernels on inputs already resident in HBM.  The end-to-end image
-rate (YOLOv8 network on MIOpen + hooks + HIP NMS, `run_e2e`) is measured in
-the same run and reported beside it under "e2e" (or alone with --e2e).
+by the HIP kernels on inputs already resident in HBM.  A plain run sets up,
+warms up, times the K steps and prints the result line.  With --full the
+end-to-end image rate (YOLOv8 network on MIOpen + hooks + HIP NMS, `run_e2e`)
+is measured in the same run and reported beside it under "e2e" (alone with
+--e2e), and so are `roofline`, `kernels`, the single-launch latency and
+`cpu_baseline`.  --dump-outputs DIR writes what the last timed step computed
+(y, bits, complexity, soft-mask tile values, channel min/max of every scale
+and batch of its launch set) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
 
 Throughput: `--pipeline D` (default 3) independent batches are in flight on D
 HIP streams, so one batch's latency-bound per-image morphology overlaps the
-HBM passes of the others; `value` = images of all K timed steps / wall time.
-`path_roofline` is the north-star figure (12 B per feature element over the
-step time); `roofline` is the dominant kernel, pass 2, timed with HIP events
-around each of its launches in single-batch steps run in sequence (the
-context `rocprofv3 ... bench.py --pipeline 1` profiles).  `cpu_baseline` is this
-package's pure-PyTorch path (fallback.py) at the same config on the host.
+HBM passes of the others; `value` = images per steady-state step time of the
+K timed steps.  `path_roofline` is the north-star figure (12 B per feature
+element over the step time); `roofline` (--full) is the dominant kernel, pass
+2, timed with HIP events around each of its launches in single-batch steps run
+in sequence (the context `rocprofv3 ... bench.py --pipeline 1` profiles).
+`cpu_baseline` (--full) is this package's pure-PyTorch path (fallback.py) at
+the same config on the host.
 
 N > 1: one process per GPU (torch.distributed.run), each rank takes its own
 batch shard (weak scaling); the per-channel batch min/max is made global with
@@ -71,6 +78,31 @@ def load_blobs(device):
     mm = torch.from_numpy(params.pack_mapper_mlp(params.sub(sd, "bit_mapper."))).to(device)
     sm = torch.from_numpy(params.pack_soft_mask(params.sub(sd, "soft_mask."))).to(device)
     return cm, mm, sm
+
+
+DUMP_SAMPLE = 1 << 20     # elements kept of a larger output (4 MB each as float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every named tensor as path/<name>.npy in float32 (float64
+    stays float64).  An output above DUMP_SAMPLE elements is written as the
+    elements at DUMP_SAMPLE flat indices drawn once from a generator seeded by
+    the output's size, so two runs (or two builds) keep the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in tensors.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(t.numel())
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit("--dump-outputs: more than %d MB of outputs" % (DUMP_MAX_BYTES >> 20))
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # BASELINE config 5: yolov8n QAT step, bs128 = 16 per GPU x 8 (weak scaling)
@@ -205,11 +237,14 @@ def main_qat(args, world, rank, dev, pg):
     core._MapperTrainFn.apply = counted
     train_step._MapperMulti.apply = counted_multi
 
+    last = {}
+
     def step():
         opt.zero_grad(set_to_none=True)
         for f in feats:
             f.grad = None
         outs, aux = h.forward_features(feats, temperature=1.0)   # curriculum stage 3: temperature 1
+        last["outs"] = outs              # (captured: the graph's own output tensors, rewritten by every replay)
         # MCAQLoss.compute_bit_budget_loss (models/mcaq_yolo.py:110-118) with weight 0.1
         lbit = h.bit_budget_loss(aux, target_bits)
         torch.autograd.backward(list(outs) + [lbit], list(G) + [w_bit])
@@ -256,51 +291,54 @@ def main_qat(args, world, rank, dev, pg):
     tpath = os.path.join(ROOT, "profiles", "pmc_traffic_config5.json")
     if os.path.exists(tpath):
         qat_traffic = {k: v["total"] for k, v in json.load(open(tpath)).get("kernels", {}).items()}
-    # per-kernel device time of the QAT quantizer over the three scales in one launch
-    L = abi.lib()
-    stream = torch.cuda.current_stream()
-    sh = abi.ctypes.c_void_p(stream.cuda_stream)
-    xs = [f.detach() for f in feats]
-    bits = [torch.rand(B, hh // grid, ww // grid, device=dev) * 6 + 2 for (hh, ww) in SIZES]
-    ms = [torch.rand(B, hh, ww, device=dev) * 0.1 + 0.9 for (hh, ww) in SIZES]
-    mm = [core._channel_minmax(x) for x in xs]
-    ys = [torch.empty_like(x) for x in xs]
-    gxs = [torch.empty_like(x) for x in xs]
-    gms = [torch.empty(B, hh, ww, device=dev) for (hh, ww) in SIZES]
-    gbs = [torch.empty_like(b) for b in bits]
-    works = [torch.empty(L.mcaq_qat_work_floats(*x.shape), device=dev) for x in xs]
-    arrive = torch.zeros(3, B * max(hh // grid for (hh, _) in SIZES), dtype=torch.int32, device=dev)
-    arr, arr_u = (abi.QatScale * 3)(), (abi.QatScale * 3)()
-    for i in range(3):
-        q = core._qat_struct(xs[i], bits[i], ms[i], mm[i][0], mm[i][1])
-        q.g, q.y, q.gx, q.gm, q.gb, q.work = core._p(G[i]), core._p(ys[i]), core._p(gxs[i]), core._p(gms[i]), \
-            core._p(gbs[i]), core._p(works[i])
-        arr_u[i] = q
-        q.arrive = core._p(arrive[i])
-        arr[i] = q
-    # each dispatch timed by its own start/stop events (hipExtLaunchKernel,
-    # mcaq_time_launch: skip 0 = the quantizer kernel, skip 1 = the fold the
-    # backward launcher issues after it), 20 launches in sequence.  The
-    # product backward folds inside its launch (arrival counters); the
-    # two-kernel form (no counters) is timed beside it for comparison.
-    kt = {}
-    reps = 20
-    for k, fn, skip in (("qat_forward", lambda: L.mcaq_qat_forward(arr_u, 3, sh), 0),
-                        ("qat_backward_kernel", lambda: L.mcaq_qat_backward(arr_u, 3, sh), 0),
-                        ("qat_fold", lambda: L.mcaq_qat_backward(arr_u, 3, sh), 1),
-                        ("qat_backward_fold_in_launch", lambda: L.mcaq_qat_backward(arr, 3, sh), 0)):
-        abi.check(fn(), k)
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-        for a_, b_ in ev:
-            a_.record(stream)
-            b_.record(stream)
-        torch.cuda.synchronize()
-        for a_, b_ in ev:
-            L.mcaq_time_launch(skip, abi.ctypes.c_void_p(a_.cuda_event), abi.ctypes.c_void_p(b_.cuda_event))
-            fn()
-        torch.cuda.synchronize()
-        kt[k] = sum(a_.elapsed_time(b_) for a_, b_ in ev) * 1e3 / reps
-    kt["qat_backward"] = kt["qat_backward_kernel"] + kt["qat_fold"]    # the product's two-kernel form
+    # per-kernel device time of the QAT quantizer over the three scales in one
+    # launch (--full only: launches of their own)
+    kt = None
+    if args.full:
+        L = abi.lib()
+        stream = torch.cuda.current_stream()
+        sh = abi.ctypes.c_void_p(stream.cuda_stream)
+        xs = [f.detach() for f in feats]
+        bits = [torch.rand(B, hh // grid, ww // grid, device=dev) * 6 + 2 for (hh, ww) in SIZES]
+        ms = [torch.rand(B, hh, ww, device=dev) * 0.1 + 0.9 for (hh, ww) in SIZES]
+        mm = [core._channel_minmax(x) for x in xs]
+        ys = [torch.empty_like(x) for x in xs]
+        gxs = [torch.empty_like(x) for x in xs]
+        gms = [torch.empty(B, hh, ww, device=dev) for (hh, ww) in SIZES]
+        gbs = [torch.empty_like(b) for b in bits]
+        works = [torch.empty(L.mcaq_qat_work_floats(*x.shape), device=dev) for x in xs]
+        arrive = torch.zeros(3, B * max(hh // grid for (hh, _) in SIZES), dtype=torch.int32, device=dev)
+        arr, arr_u = (abi.QatScale * 3)(), (abi.QatScale * 3)()
+        for i in range(3):
+            q = core._qat_struct(xs[i], bits[i], ms[i], mm[i][0], mm[i][1])
+            q.g, q.y, q.gx, q.gm, q.gb, q.work = core._p(G[i]), core._p(ys[i]), core._p(gxs[i]), core._p(gms[i]), \
+                core._p(gbs[i]), core._p(works[i])
+            arr_u[i] = q
+            q.arrive = core._p(arrive[i])
+            arr[i] = q
+        # each dispatch timed by its own start/stop events (hipExtLaunchKernel,
+        # mcaq_time_launch: skip 0 = the quantizer kernel, skip 1 = the fold the
+        # backward launcher issues after it), 20 launches in sequence.  The
+        # product backward folds inside its launch (arrival counters); the
+        # two-kernel form (no counters) is timed beside it for comparison.
+        kt = {}
+        reps = 20
+        for k, fn, skip in (("qat_forward", lambda: L.mcaq_qat_forward(arr_u, 3, sh), 0),
+                            ("qat_backward_kernel", lambda: L.mcaq_qat_backward(arr_u, 3, sh), 0),
+                            ("qat_fold", lambda: L.mcaq_qat_backward(arr_u, 3, sh), 1),
+                            ("qat_backward_fold_in_launch", lambda: L.mcaq_qat_backward(arr, 3, sh), 0)):
+            abi.check(fn(), k)
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+            for a_, b_ in ev:
+                a_.record(stream)
+                b_.record(stream)
+            torch.cuda.synchronize()
+            for a_, b_ in ev:
+                L.mcaq_time_launch(skip, abi.ctypes.c_void_p(a_.cuda_event), abi.ctypes.c_void_p(b_.cuda_event))
+                fn()
+            torch.cuda.synchronize()
+            kt[k] = sum(a_.elapsed_time(b_) for a_, b_ in ev) * 1e3 / reps
+        kt["qat_backward"] = kt["qat_backward_kernel"] + kt["qat_fold"]    # the product's two-kernel form
 
     if pg is not None:
         import torch.distributed as dist
@@ -314,14 +352,23 @@ def main_qat(args, world, rank, dev, pg):
     step_s = (time.perf_counter() - t0) / args.steps
     core._MapperTrainFn.apply = orig_apply
     train_step._MapperMulti.apply = orig_multi
+    if args.dump_outputs and rank == 0:
+        # the last timed step: quantized features, feature gradients, and the
+        # hook parameters as its optimizer step left them
+        dump = {"scale%d_y" % i: o for i, o in enumerate(last["outs"])}
+        dump.update({"scale%d_grad_x" % i: f.grad for i, f in enumerate(feats) if f.grad is not None})
+        dump.update({"param." + n: p for n, p in h.named_parameters() if p.requires_grad})
+        dump_outputs(args.dump_outputs, dump)
     # one step alone (device idle before it): its latency, and how long the
     # host takes to issue it
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    run()
-    t_one_enq = time.perf_counter() - t1
-    torch.cuda.synchronize()
-    t_one = time.perf_counter() - t1
+    t_one = t_one_enq = None
+    if args.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run()
+        t_one_enq = time.perf_counter() - t1
+        torch.cuda.synchronize()
+        t_one = time.perf_counter() - t1
     fused_per_step = fused["calls"] / max(1, args.steps + max(args.warmup, 3)) if not use_graph else None
     if pg is not None:
         import torch.distributed as dist
@@ -337,7 +384,7 @@ def main_qat(args, world, rank, dev, pg):
         fold_b = sum(4 * 2 * ((c + 31) // 32) * B * hh * ww for c, (hh, ww) in zip(chans, SIZES)) + 4 * pix
         for k, nb in (("qat_forward", 8 * elems + 4 * pix), ("qat_backward_kernel", 12 * elems + 4 * pix),
                       ("qat_fold", fold_b), ("qat_backward", 12 * elems + 4 * pix),
-                      ("qat_backward_fold_in_launch", 12 * elems + 4 * pix)):
+                      ("qat_backward_fold_in_launch", 12 * elems + 4 * pix)) if args.full else ():
             gbs_ = nb / (kt[k] * 1e-6) / 1e9
             kern[k] = {"us": round(kt[k], 2), "alg_bytes": nb, "GB/s": round(gbs_, 1),
                        "frac": round(gbs_ / HBM_PEAK_GBS, 4)}
@@ -356,9 +403,9 @@ def main_qat(args, world, rank, dev, pg):
                        "scales": _qat_scales_mode(h, feats),
                        "optimizer": opt_kind + " (train.py:626-641)",
                        "host_enqueue_us_per_step": round(t_enq / args.steps * 1e6, 1),
-                       "single_step_latency_us": round(t_one * 1e6, 1),
-                       "single_step_enqueue_us": round(t_one_enq * 1e6, 1)},
-            "roofline": {"bound": "hbm", "achieved": kern["qat_backward_kernel"]["GB/s"], "peak": HBM_PEAK_GBS,
+                       "single_step_latency_us": round(t_one * 1e6, 1) if args.full else None,
+                       "single_step_enqueue_us": round(t_one_enq * 1e6, 1) if args.full else None},
+            "roofline": None if not args.full else {"bound": "hbm", "achieved": kern["qat_backward_kernel"]["GB/s"], "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": kern["qat_backward_kernel"]["frac"],
                          "traffic": qat_traffic.get("mcaq_qat_kernel<bwd>"),
                          "kernel": "mcaq_qat_kernel<bwd> (read g, x + write grad_x: 12 B per element, + 4 B per "
@@ -369,13 +416,13 @@ def main_qat(args, world, rank, dev, pg):
                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
                               "kernel": "whole QAT step, 24 B per feature element (fwd 12 + bwd 12)",
                               "alg_bytes_per_step": 24 * elems},
-            "kernels": kern,
+            "kernels": kern if args.full else None,
             "cpu_baseline": None,
             "mapper": {"fused_kernels": fused["calls"] > 0,
                        "batchnorm": type(h.bit_mapper.mapping_network[1]).__name__,
                        "fused_calls_per_eager_step": fused_per_step},
         }
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline_qat()
         print(json.dumps(out), flush=True)
     if pg is not None:
@@ -417,7 +464,7 @@ def _shift_class_bias(m, imgs, target=E2E_TARGET_CANDIDATES):
 
 
 def run_e2e(cfg, steps, warmup, world, rank, dev, pg, amp=False, eager=False, fuse=True, channels_last=False,
-            inflight=2):
+            inflight=2, full=True, dump=None):
     """End-to-end MCAQ inference: YOLOv8 (MIOpen
     convolutions, seeded weights) with the MCAQ hooks at C3/C4/C5 on the HIP
     kernels, Detect decode, batched HIP NMS; N > 1: each rank its batch shard,
@@ -490,7 +537,8 @@ def run_e2e(cfg, steps, warmup, world, rank, dev, pg, amp=False, eager=False, fu
 
     runs = {}
     with torch.no_grad():
-        for hooks in (True, False):
+        # full: the network without the hooks is timed too (the hooks' share)
+        for hooks in (True, False) if full else (True,):
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -530,9 +578,12 @@ def run_e2e(cfg, steps, warmup, world, rank, dev, pg, amp=False, eager=False, fu
                 sync = lambda: None
             torch.cuda.synchronize()
             runs[hooks] = (timed(fn, steps, sync), res)
+            if hooks and dump and rank == 0:
+                # slot 0's detections (padded rows, counts) as its last timed replay left them
+                dump_outputs(dump, {"detections": res[0], "counts": res[1]})
     m.plan_slot = 0
     step_s, (out, cnt) = runs[True]
-    net_s = runs[False][0]
+    net_s = runs[False][0] if full else None
     return {
         "metric": E2E_METRIC, "value": round(world * B / step_s, 2), "unit": "images/s", "n_gpus": world,
         "steps": steps, "warmup": warmup, "ms_per_step": round(step_s * 1e3, 4), "higher_is_better": True,
@@ -547,10 +598,10 @@ def run_e2e(cfg, steps, warmup, world, rank, dev, pg, amp=False, eager=False, fu
                    "parallelism": "dp%d" % world, "hip_graph": use_graph,
                    "rccl_in_graph": use_graph and pg is not None,
                    "conv_bn_fused": fuse, "channels_last": channels_last, "batches_in_flight": nin,
-                   "network_only_ms_per_step": round(net_s * 1e3, 4),
+                   "network_only_ms_per_step": round(net_s * 1e3, 4) if full else None,
                    # both legs run NMS: the difference is the hooks' cost per step
-                   "mcaq_hooks_ms_per_step": round((step_s - net_s) * 1e3, 4),
-                   "hook_share_of_step": round((step_s - net_s) / step_s, 4),
+                   "mcaq_hooks_ms_per_step": round((step_s - net_s) * 1e3, 4) if full else None,
+                   "hook_share_of_step": round((step_s - net_s) / step_s, 4) if full else None,
                    "detections_per_image": round(float(cnt.float().mean()), 2)},
     }
 
@@ -603,7 +654,9 @@ def main_score(args, world, rank, dev, pg):
                                   "global scratch), scores kept on the device" % bs,
                       "global_batch": world * bs, "parallelism": "dp%d" % world},
            "cpu_baseline": None}
-    if rank == 0 and not args.no_cpu and world == 1:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": out[args.steps - 1]})
+    if rank == 0 and args.full and not args.no_cpu and world == 1:
         threads = int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1)
         torch.set_num_threads(threads)
         ac = core.MorphologicalComplexityAnalyzer(device="cpu", grid_size=8)
@@ -630,7 +683,7 @@ def main_e2e(args, world, rank, dev, pg):
     if args.find:
         torch.backends.cudnn.benchmark = True
     out = run_e2e(args.config, args.steps, args.warmup, world, rank, dev, pg, args.amp, args.eager,
-                  not args.no_fuse, args.channels_last, args.e2e_inflight)
+                  not args.no_fuse, args.channels_last, args.e2e_inflight, full=args.full, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if pg is not None:
@@ -869,8 +922,15 @@ def main():
     ap.add_argument("--inputs", type=int, default=0,
                     help="distinct input batches cycled through (default max(3, pipeline): >= 276 MB of x at "
                          "config 2, more than the 256 MiB Infinity Cache, so no step finds its input cached)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (YOLOv8 + hooks + NMS) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the per-kernel / roofline timings, the single-launch latency, "
+                         "the end-to-end leg and the cpu_baseline (off by default: a plain run sets up, warms up, "
+                         "times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; outputs above 2^20 elements as a fixed, seeded sample)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end (YOLOv8 + hooks + NMS) leg")
     ap.add_argument("--e2e", action="store_true", help="only the end-to-end line (run_e2e)")
     ap.add_argument("--torch-optim", action="store_true",
                     help="--config 5: torch clip_grad_norm_ + fused AdamW + projection instead of optim.ClipAdamW")
@@ -991,28 +1051,32 @@ def main():
     # per-kernel device times: in sequence (pass 2 right behind its own pass 1
     # and morphology) and with x evicted from the Infinity Cache before each
     # timed HBM pass (the roofline figure)
-    kt_seq = kernel_timing(plans)
-    sweep = torch.ones(96 << 20, device=dev)         # 384 MiB
-    kt = kernel_timing(plans, evict=sweep)
-    del sweep
-    # single-batch latency: one batch through its chain with nothing in flight
-    # beside it (the plan's own launch sequence on one stream)
-    lat = []
-    for _ in range(10):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        plans[0].launch(torch.cuda.current_stream())
-        torch.cuda.synchronize()
-        lat.append(time.perf_counter() - t1)
-    latency_ms = sorted(lat)[len(lat) // 2] * 1e3
-    runner.run(4 * nbat)  # plans[0] was re-run alone: a few more steps to be safe, then settle
-    runner.sync()
+    # (--full only: they take runs of their own)
+    kt_seq = kt = latency_ms = None
+    if args.full:
+        kt_seq = kernel_timing(plans)
+        sweep = torch.ones(96 << 20, device=dev)         # 384 MiB
+        kt = kernel_timing(plans, evict=sweep)
+        del sweep
+        # single-batch latency: one batch through its chain with nothing in flight
+        # beside it (the plan's own launch sequence on one stream)
+        lat = []
+        for _ in range(10):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            plans[0].launch(torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t1)
+        latency_ms = sorted(lat)[len(lat) // 2] * 1e3
+        runner.run(4 * nbat)  # plans[0] was re-run alone: a few more steps to be safe, then settle
+        runner.sync()
 
-    # ---- timed region: K steps, `depth` batches in flight.  Every window
-    # starts and ends synchronised, so it carries one pipeline fill and one
-    # drain (~ one batch's chain latency).  Two windows, K and 2K steps: their
-    # difference is K steady-state steps (the fill and drain cancel), which
-    # is what ms_per_step reports; the raw K-step window is kept beside it.
+    # ---- timed region: the K steps, `depth` batches in flight, as two
+    # windows of K1 and K2 = K - K1 steps.  Every window starts and ends
+    # synchronised, so it carries one pipeline fill and one drain (~ one
+    # batch's chain latency).  The windows' difference is K2 - K1 steady-state
+    # steps (the fill and drain cancel), which is what ms_per_step reports;
+    # the raw figure of all K steps is kept beside it.
     def window(k):
         runner.sync()
         if pg is not None:
@@ -1033,21 +1097,41 @@ def main():
             wall = float(t.item())
         return wall, t_enq
 
-    # the K / 2K pair is repeated (5 pairs up to K = 100, else 3) and the
-    # median slope reported: one host hiccup in a short window otherwise moves
-    # the slope by several %; the first K-step window stays the raw figure
-    npairs = 5 if args.steps <= 100 else 3
-    slopes = []
-    for i in range(npairs):
-        wk, te = window(args.steps)
-        w2k, _ = window(2 * args.steps)
-        if i == 0:
-            wall_k, t_enq, wall_2k = wk, te, w2k
-        slopes.append((w2k - wk) / args.steps)
-    step_s = sorted(slopes)[npairs // 2]
-    if step_s <= 0.0:          # clock noise: fall back to the raw window
-        step_s = wall_k / args.steps
-    quant_us = kt["quant"]
+    # --steps sets the timed steps: K1 + K2 = K.  K1 is a third of the launch
+    # sets (at least `depth`, so both windows fill the pipeline); with fewer
+    # than 2 * depth + 1 launch sets there is one window and the raw figure
+    sets = args.steps // nbat
+    k1 = max(depth, sets // 3) * nbat
+    k2 = args.steps - k1
+    if k2 > k1:
+        wall_1, te1 = window(k1)
+        wall_2, te2 = window(k2)
+        t_enq = te1 + te2
+        step_s = (wall_2 - wall_1) / (k2 - k1)
+        timing = "steady state: (wall(%d steps) - wall(%d steps)) / %d, the K = %d timed steps in two windows, " \
+                 "each synchronised on both sides (the pipeline fill and drain cancel)" % (k2, k1, k2 - k1, args.steps)
+    else:
+        k1, k2 = 0, args.steps
+        wall_1 = 0.0
+        wall_2, t_enq = window(k2)
+        step_s = 0.0
+        timing = "one synchronised window of the K = %d timed steps (with its pipeline fill and drain)" % args.steps
+    raw_s = (wall_1 + wall_2) / args.steps
+    if step_s <= 0.0:          # one window, or clock noise: the raw figure
+        step_s = raw_s
+    dump = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's launch set (the plan the runner issued last)
+        last = plans[(runner.i - 1) % len(plans)]
+        dump = {}
+        for k in range(nbat):
+            for si, b in enumerate(last.batch_bufs(k)):
+                lo, hi = last.channel_minmax(si * nbat + k)
+                for key, t in (("y", b["y"]), ("bits", b["bits"]), ("complexity", b["complexity"]),
+                               ("soft_mask_tiles", b["mt"]), ("channel_min", lo), ("channel_max", hi)):
+                    dump["batch%d_scale%d_%s" % (k, si, key)] = t
+        dump_outputs(args.dump_outputs, dump)
+        del dump
 
     elems = sum(B * c * h * w for c, (h, w) in zip(chans, SIZES))    # per batch (= per step)
     lelems = nbat * elems                                            # per kernel launch
@@ -1064,7 +1148,9 @@ def main():
     achieved = alg_bytes / step_s / 1e9
     value = world * B / step_s
     out = None
-    if rank == 0:
+    kern = roofline = None
+    if rank == 0 and args.full:
+        quant_us = kt["quant"]
         q_gbs = 8 * lelems / (quant_us * 1e-6) / 1e9
         seq = "hipExtLaunchKernel start/stop events of each launch, median of 40 single-launch steps in sequence " \
               "on one stream over %d input launch sets (%d batch(es) each), x evicted from the Infinity Cache " \
@@ -1078,6 +1164,16 @@ def main():
                          "us_in_sequence": round(kt_seq["stats"], 2)}
         kern["morph_finalize"] = {"us": round(kt_seq["morph_finalize"], 2), "bound": "latency (per-image chain)",
                                   "timing": "events around the launch, in sequence"}
+        # the dominant kernel (pass 2): algorithmic bytes per launch over its
+        # launch time (HIP events on its stream, single-batch steps in sequence)
+        roofline = {"bound": "hbm", "achieved": kern["quant"]["GB/s"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": kern["quant"]["frac"],
+                    "traffic": traffic_k.get("mcaq_quant_tile_kernel", traffic_k.get("mcaq_quant_kernel")),
+                    "kernel": "%s (pass 2: read x + write y, 8 B per feature element)"
+                              % ("mcaq_quant_tile_kernel" if "mcaq_quant_tile_kernel" in traffic_k
+                                 else "mcaq_quant_kernel"),
+                    "alg_bytes_per_launch": 8 * lelems, "us_per_launch": kern["quant"]["us"]}
+    if rank == 0:
         out = {
             "metric": HOOK_METRIC,
             "value": round(value, 2),
@@ -1107,13 +1203,11 @@ def main():
                        "schedule": "streams: %d launch-set chains (%d independent batch(es) per launch, each with "
                                    "its own statistics) on %d streams, one HIP graph each" % (depth, nbat, depth),
                        "input_batches": len(plans) * nbat,
-                       "latency_ms_single_launch": round(latency_ms, 4),
+                       "latency_ms_single_launch": None if latency_ms is None else round(latency_ms, 4),
                        "host_enqueue_us_per_step": round(t_enq / args.steps * 1e6, 1),
-                       "timing": "steady state: median over %d pairs of (wall(2K steps) - wall(K steps)) / K, "
-                                 "each window synchronised on both sides (the pipeline fill and drain cancel)" % npairs,
-                       "slopes_ms_per_step": [round(x * 1e3, 5) for x in slopes],
-                       "raw_window_ms_per_step": round(wall_k / args.steps * 1e3, 5),
-                       "raw_window_2k_ms_per_step": round(wall_2k / (2 * args.steps) * 1e3, 5)},
+                       "timing": timing,
+                       "window_steps": [k1, k2],
+                       "raw_window_ms_per_step": round(raw_s * 1e3, 5)},
             # north star: the whole fused complexity + quant path,
             # 12 B per feature element over the wall time of a step
             "path_roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1121,19 +1215,11 @@ def main():
                               "kernel": "whole step: mcaq_stats + mcaq_morph_kernel + mcaq_tiles_kernel + "
                                         "mcaq_quant, 12 B per feature element per step",
                               "alg_bytes_per_step": alg_bytes},
-            # the dominant kernel (pass 2): algorithmic bytes per launch over its
-            # launch time (HIP events on its stream, single-batch steps in sequence)
-            "roofline": {"bound": "hbm", "achieved": kern["quant"]["GB/s"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": kern["quant"]["frac"],
-                         "traffic": traffic_k.get("mcaq_quant_tile_kernel", traffic_k.get("mcaq_quant_kernel")),
-                         "kernel": "%s (pass 2: read x + write y, 8 B per feature element)"
-                                   % ("mcaq_quant_tile_kernel" if "mcaq_quant_tile_kernel" in traffic_k
-                                      else "mcaq_quant_kernel"),
-                         "alg_bytes_per_launch": 8 * lelems, "us_per_launch": kern["quant"]["us"]},
-            "kernels": kern,
+            "roofline": roofline,          # --full
+            "kernels": kern,               # --full
             "cpu_baseline": None,
         }
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         for p_ in plans:
             p_.feats = None
         del runner
@@ -1146,7 +1232,7 @@ def main():
             if out is not None:
                 out["e2e"] = {"error": repr(exc)[:300]}
     if rank == 0:
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(out), flush=True)
     if pg is not None:

@@ -14,11 +14,11 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout
 rc=$?; grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -1; [ $rc -eq 0 ] || { grep -E "FAIL|Error|assert" $OUT/pytest_gpu.log | head -30; exit $rc; }
 timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
 tail -2 $OUT/smoke.log
-timeout -k 10 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
-timeout -k 10 300 python bench.py --config 5 > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -5 $OUT/bench_config5.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 5 > $OUT/bench_config5.json 2> $OUT/bench_config5.err || { tail -5 $OUT/bench_config5.err; exit 1; }
 MCAQ_BENCH_SHARDED=1 timeout -k 10 300 python bench.py --config 5 --no-cpu > $OUT/bench_config5_sharded.json 2> $OUT/bench_config5_sharded.err || { tail -5 $OUT/bench_config5_sharded.err; exit 1; }
-timeout -k 10 300 python bench.py --e2e --amp --steps 20 --warmup 3 > $OUT/bench_e2e_amp.json 2> $OUT/bench_e2e_amp.err || { tail -5 $OUT/bench_e2e_amp.err; exit 1; }
-MCAQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --no-cpu --steps 20 --warmup 4 > $OUT/bench_gloo_n2.json 2> $OUT/bench_gloo_n2.err || { tail -5 $OUT/bench_gloo_n2.err; exit 1; }
+timeout -k 10 300 python bench.py --full --e2e --amp --steps 20 --warmup 3 > $OUT/bench_e2e_amp.json 2> $OUT/bench_e2e_amp.err || { tail -5 $OUT/bench_e2e_amp.err; exit 1; }
+MCAQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --no-cpu --steps 20 --warmup 4 > $OUT/bench_gloo_n2.json 2> $OUT/bench_gloo_n2.err || { tail -5 $OUT/bench_gloo_n2.err; exit 1; }
 MCAQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 4 --no-cpu --no-e2e --steps 20 --warmup 4 > $OUT/bench_gloo_n4.json 2> $OUT/bench_gloo_n4.err || { tail -5 $OUT/bench_gloo_n4.err; exit 1; }
 MCAQ_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 4 --config 5 --no-cpu --steps 10 --warmup 3 > $OUT/bench_gloo_n4_c5.json 2> $OUT/bench_gloo_n4_c5.err || { tail -5 $OUT/bench_gloo_n4_c5.err; exit 1; }
 prof() {  # name, bench args...

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 tail -3 $OUT/pytest_ls.log
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 240 python -u bench.py --no-cpu --no-e2e --steps 120 "$@" > $OUT/b_$n.json 2> $OUT/b_$n.err || { echo "FAIL $n"; tail -5 $OUT/b_$n.err; exit 1; }
+  timeout -k 10 240 python -u bench.py --full --no-cpu --no-e2e --steps 120 "$@" > $OUT/b_$n.json 2> $OUT/b_$n.err || { echo "FAIL $n"; tail -5 $OUT/b_$n.err; exit 1; }
   python - "$OUT/b_$n.json" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -16,7 +16,7 @@ b c2 python -u bench.py --no-cpu --no-e2e --steps 120
 b c2_sharded MCAQ_BENCH_SHARDED=1 python -u bench.py --no-cpu --no-e2e --steps 120
 b c5 python -u bench.py --config 5 --no-cpu --steps 100
 b c5_torchopt python -u bench.py --config 5 --no-cpu --steps 100 --torch-optim
-b score python -u bench.py --score --steps 10 --warmup 2
+b score python -u bench.py --full --score --steps 10 --warmup 2
 b c5_sharded MCAQ_BENCH_SHARDED=1 python -u bench.py --config 5 --no-cpu --steps 100
 for c in 2 5; do
   MCAQ_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29500 + c)) bench.py --gpus 2 --config $c --steps 10 --warmup 4 --no-cpu --no-e2e > $OUT/gloo_n2_config$c.json 2> $OUT/gloo_n2_config$c.err || { tail -20 $OUT/gloo_n2_config$c.err; exit 1; }

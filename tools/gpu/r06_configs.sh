@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $R
 for c in 3 4; do
   for k in 1 2; do
-    timeout -k 10 400 python bench.py --config $c --no-cpu --no-e2e --launch-batches $k > $OUT/b_c${c}_k$k.json 2> $OUT/b_c${c}_k$k.err || { tail -5 $OUT/b_c${c}_k$k.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --config $c --no-cpu --no-e2e --launch-batches $k > $OUT/b_c${c}_k$k.json 2> $OUT/b_c${c}_k$k.err || { tail -5 $OUT/b_c${c}_k$k.err; exit 1; }
   done
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/c${c}_p1 -o run --output-format csv -- python3 $R/bench.py --config $c --no-cpu --no-e2e --pipeline 1 --launch-batches 1 --steps 60 > $OUT/c${c}_p1.log 2>&1) || { tail -8 $OUT/c${c}_p1.log; exit 1; }
   cp $OUT/c${c}_p1/run_kernel_stats.csv $OUT/kernel_stats_c${c}_p1_k1.csv

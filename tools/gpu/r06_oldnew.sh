@@ -10,7 +10,7 @@ O=$R/gpurun_out/r06_oldnew
 mkdir -p $O
 for r in 1 2 3; do
   (cd $R/tools/probe/ab/oldtree && timeout -k 10 200 python bench.py --no-cpu --no-e2e > $O/old_$r.json 2> $O/old_$r.err) || { tail -5 $O/old_$r.err; exit 1; }
-  (cd $R && timeout -k 10 200 python bench.py --no-cpu --no-e2e > $O/new_$r.json 2> $O/new_$r.err) || { tail -5 $O/new_$r.err; exit 1; }
+  (cd $R && timeout -k 10 200 python bench.py --full --no-cpu --no-e2e > $O/new_$r.json 2> $O/new_$r.err) || { tail -5 $O/new_$r.err; exit 1; }
   python3 -c "
 import json
 for v in ('old', 'new'):
