@@ -170,7 +170,7 @@ size_t mcaq_morph_work_bytes(int B, int Hc, int Wc, int tile);
 /* ---- pass 2: y = dequant(quant_b(x)) * m ----------------------------------- */
 typedef struct {
   const float* x;      /* (B, C, H, W), element type `dtype` */
-  float* y;            /* (B, C, H, W), element type `ydtype` */
+  float* y;            /* (B, C, H, W), fp32 */
   const float* bits;   /* (B, ht, wt) integer-valued */
   const float* m;      /* (B, H, W) or NULL */
   const float* mt;     /* (B, ht, wt) soft-mask tile values: when set, m(p) is
@@ -192,9 +192,9 @@ typedef struct {
   int dtype;           /* element type of x (MCAQ_DTYPE_*, one per launch): fp16 / bf16
                           maps widen exactly and the arithmetic is fp32; they take
                           the tile-aligned kernel only (otherwise hipErrorNotSupported) */
-  int ydtype;          /* element type of y: dtype, or MCAQ_DTYPE_F32 (the reference's
-                          promotion: an fp16 map times the fp32 soft mask is fp32,
-                          quantization.py:742-744); rounded to nearest even */
+  int ydtype;          /* element type of y: MCAQ_DTYPE_F32 only (the reference's result
+                          type on fp16 / bf16 maps too: its fp32 tile mask promotes
+                          the sum, quantization.py:732-738); else hipErrorInvalidValue */
 } mcaq_quant_scale;
 int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream);
 

@@ -145,16 +145,13 @@ __device__ __forceinline__ void wave_minmax16(float (&mn)[ST_CG], float (&mx)[ST
 // ---- feature element types (MCAQ_DTYPE_*): fp32, or the fp16 / bf16 maps an
 // autocast region hands the hooks.  Loads widen exactly to fp32 (all
 // arithmetic stays fp32: the analyzer's gray / |x| sums are those of
-// x.float(), morphology.py:834-837); stores round to nearest even.
+// x.float(), morphology.py:834-837).  y is always fp32, the reference's
+// result type on a half map (quantization.py:736-738: the fp32 tile mask
+// promotes the sum), so only fp32 has a store.
 typedef float mcaq_f4v __attribute__((ext_vector_type(4)));
 typedef _Float16 mcaq_h4v __attribute__((ext_vector_type(4)));
 typedef unsigned short mcaq_u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float bf16_f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
-__device__ __forceinline__ unsigned short f_bf16(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);   // quiet NaN
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 // The nontemporal choice is a template argument: a runtime `nt ? ntload(p)
 // : *p` lets LLVM merge the two loads of one address and drop the
 // nontemporal bit (round 6: pass 1's x loads lost `nt` that way, -10 % on
@@ -186,9 +183,6 @@ template <> struct ElemIO<_Float16> {
     return __builtin_convertvector(ld_v<NT>(reinterpret_cast<const mcaq_h4v*>(p)), mcaq_f4v);
   }
   static __device__ __forceinline__ float2 ld2(const _Float16* p) { return make_float2((float)p[0], (float)p[1]); }
-  template <bool NT> static __device__ __forceinline__ void st4(_Float16* p, mcaq_f4v v) {
-    st_v<NT>(reinterpret_cast<mcaq_h4v*>(p), __builtin_convertvector(v, mcaq_h4v));
-  }
 };
 struct Bf16 { unsigned short u; };
 template <> struct ElemIO<Bf16> {
@@ -198,9 +192,6 @@ template <> struct ElemIO<Bf16> {
     return mcaq_f4v{bf16_f(u.x), bf16_f(u.y), bf16_f(u.z), bf16_f(u.w)};
   }
   static __device__ __forceinline__ float2 ld2(const Bf16* p) { return make_float2(bf16_f(p[0].u), bf16_f(p[1].u)); }
-  template <bool NT> static __device__ __forceinline__ void st4(Bf16* p, mcaq_f4v v) {
-    st_v<NT>(reinterpret_cast<mcaq_u4v*>(p), mcaq_u4v{f_bf16(v.x), f_bf16(v.y), f_bf16(v.z), f_bf16(v.w)});
-  }
 };
 
 // Fold one 16-row block sum into cascade levels a1..a3 (Cascade::push at i % 16 == 0).
@@ -1917,8 +1908,7 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
         scales[i].ht < 1 || scales[i].wt < 1 || !scales[i].x || !scales[i].y || !scales[i].bits ||
         !scales[i].xmin || !scales[i].xmax || scales[i].dtype != scales[0].dtype ||
         scales[i].dtype < MCAQ_DTYPE_F32 || scales[i].dtype > MCAQ_DTYPE_BF16 ||
-        scales[i].ydtype != scales[0].ydtype ||
-        (scales[i].ydtype != scales[i].dtype && scales[i].ydtype != MCAQ_DTYPE_F32))
+        scales[i].ydtype != MCAQ_DTYPE_F32)
       return (int)hipErrorInvalidValue;
     units += scales[i].B * ((HW + 255) / 256) * ((scales[i].C + QSLICE - 1) / QSLICE);
   }
@@ -1986,15 +1976,10 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     // NT loads and stores)
     if (!tile_ok) return (int)hipErrorNotSupported;
     const dim3 g(MCAQ_STREAM_CAP > 0 ? imin_(units, MCAQ_STREAM_CAP * 256) : units);
-    const bool yf = scales[0].ydtype == MCAQ_DTYPE_F32;
-    switch ((kind == QM_NONE ? 0 : 1) + (dt == MCAQ_DTYPE_BF16 ? 2 : 0) + (yf ? 4 : 0)) {
-      case 0: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, _Float16>, g, t, 0, stream, a); break;
-      case 1: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, _Float16>, g, t, 0, stream, a); break;
-      case 2: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, Bf16>, g, t, 0, stream, a); break;
-      case 3: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, Bf16>, g, t, 0, stream, a); break;
-      case 4: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, _Float16, float>, g, t, 0, stream, a); break;
-      case 5: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, _Float16, float>, g, t, 0, stream, a); break;
-      case 6: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, Bf16, float>, g, t, 0, stream, a); break;
+    switch ((kind == QM_NONE ? 0 : 1) + (dt == MCAQ_DTYPE_BF16 ? 2 : 0)) {
+      case 0: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, _Float16, float>, g, t, 0, stream, a); break;
+      case 1: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, _Float16, float>, g, t, 0, stream, a); break;
+      case 2: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, Bf16, float>, g, t, 0, stream, a); break;
       default: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, Bf16, float>, g, t, 0, stream, a); break;
     }
     return (int)hipGetLastError();

@@ -58,9 +58,10 @@ def _require_cuda(*ts):
 # MCAQ_DTYPE_*): fp32, and the fp16 / bf16 maps an autocast region hands the
 # hooks (train.py:582-585, 748-749).  fp16 / bf16 widen exactly in pass 1 and
 # pass 2, all arithmetic is fp32 (the analyzer's gray / |x| sums are those of
-# x.float(), morphology.py:834-837).  y takes the reference's result type: the
-# input's dtype, or fp32 where the fp32 soft mask multiplies it
-# (quantization.py:742-744 promotes fp16 * fp32 to fp32).
+# x.float(), morphology.py:834-837).  y takes the reference's result type,
+# which is fp32 for every map: its inference branch sums x_q * mask with the
+# fp32 nearest tile mask (quantization.py:732-738), which promotes fp16 / bf16
+# with or without the soft mask (tests/golden/amp_types.npz).
 _DTYPES = {torch.float32: abi.DTYPE_F32, torch.float16: abi.DTYPE_F16, torch.bfloat16: abi.DTYPE_BF16}
 
 
@@ -68,7 +69,8 @@ def half_native_ok(geom, min_bits=2.0, max_bits=8.0):
     """True when pass 2 takes an fp16 / bf16 map of this geometry natively
     (the tile-aligned kernel: the map a power-of-two multiple of the tile
     grid, tiles >= 4 pixels wide, H*W % 4 == 0, <= 1024 tiles, <= 8 widths);
-    otherwise callers quantize x.float()."""
+    otherwise callers quantize x.float().  The map's base must also be 16-byte
+    aligned (half_aligned)."""
     def pow2_mult(n, t):
         k = 0
         while (t << k) < n:
@@ -78,6 +80,13 @@ def half_native_ok(geom, min_bits=2.0, max_bits=8.0):
     okw, sw = pow2_mult(geom.W, geom.wt)
     return okh and okw and sw >= 2 and (geom.H * geom.W) % 4 == 0 and geom.ht * geom.wt <= 1024 and \
         int(max_bits) - int(min_bits) + 1 <= 8
+
+
+def half_aligned(t):
+    """True when an fp16 / bf16 map starts on the 16 bytes the tile-aligned
+    kernel's rows need (mcaq_quant's `vec`): a contiguous view may start at
+    any element of its storage.  Otherwise callers quantize x.float()."""
+    return t.data_ptr() % 16 == 0
 
 
 def _stream_handle(stream):
@@ -257,10 +266,8 @@ class HookPlan:
         if dtype != torch.float32:
             if m_plane or not all(half_native_ok(g, min_bits, max_bits) for g in self.geoms):
                 raise ValueError("%s feature maps need the tile-aligned quantizer (engine.half_native_ok)" % dtype)
-        ydt = [torch.float32 if (sm is not None and quantize) else dtype for sm in smasks]
-        for b, g, yd in zip(self.bufs, self.geoms, ydt):
-            if b["y"].dtype != yd:          # y in the reference's result type
-                b["y"] = torch.empty(g.B, g.C, g.H, g.W, device=self.device, dtype=yd)
+            if not all(half_aligned(f) for f in feats):
+                raise ValueError("%s feature maps need a 16-byte aligned base (engine.half_aligned)" % dtype)
         # descriptor reuse: an eager hook calls prepare once per forward with
         # new x / output tensors and otherwise the same blobs, buffers and
         # options; then only those pointers are patched into the structs
@@ -371,7 +378,7 @@ class HookPlan:
                 s.stats_cover_x = 1 if (minmax is None or minmax[i] is None) else 0
                 s.neg_min = 1 if self._neg else 0
                 s.dtype = _DTYPES[dtype]
-                s.ydtype = _DTYPES[b["y"].dtype]
+                s.ydtype = abi.DTYPE_F32      # the reference's result type on every map
             self._qs = qs
         self._n = n
         self._sig = sig

@@ -234,13 +234,15 @@ class MCAQHooks(nn.Module):
         quantize = state.get("quantize", True)
         quantizer = self.quantizers[str(layer_idx)]
         # fp16 / bf16 maps (an autocast region) are read natively by pass 1 and
-        # pass 2 (fp32 arithmetic, y in the input's dtype) where the quantizer's
-        # tile-aligned kernel takes the shape; otherwise quantized as x.float()
+        # pass 2 (fp32 arithmetic; y is fp32, the reference's result type) where
+        # the quantizer's tile-aligned kernel takes the shape and the map's base
+        # is 16-byte aligned; otherwise quantized as x.float()
         half = feat.dtype in (torch.float16, torch.bfloat16)
         x = feat.contiguous() if half else feat.float().contiguous()
         plan = self._plan(x)
-        if half and not all(engine.half_native_ok(g, self.bit_mapper.min_bits, self.bit_mapper.max_bits)
-                            for g in plan.geoms):
+        if half and not (engine.half_aligned(x) and
+                         all(engine.half_native_ok(g, self.bit_mapper.min_bits, self.bit_mapper.max_bits)
+                             for g in plan.geoms)):
             x = x.float()
         if state.get("calibrating", False) and quantize:
             quantizer.update_running_stats(x.float())
