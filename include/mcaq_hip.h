@@ -44,7 +44,7 @@ typedef void* hipEvent_t;
 extern "C" {
 #endif
 
-#define MCAQ_ABI_VERSION 28
+#define MCAQ_ABI_VERSION 29
 /* feature-map element types (mcaq_stats_scale.dtype, mcaq_quant_scale.dtype) */
 #define MCAQ_DTYPE_F32 0
 #define MCAQ_DTYPE_F16 1
@@ -153,6 +153,13 @@ typedef struct {
                         adaptive binarize, tile 4/8/16, map <= 128 x 128), pass
                         A runs as one workgroup per 16-row band + one per
                         image instead of one whole-CU workgroup per image. */
+  int smask_arith;   /* 0: the soft mask's side information in fp32 (the default);
+                        MCAQ_DTYPE_F16 / _BF16: in the reference's arithmetic on a
+                        map of that type (quantization.py:226-228): the channel
+                        mean of |x| (the fp32 absmean plane of pass 1), the tile
+                        mean and act / (amax + 1e-8) are each rounded once to that
+                        type; the soft-mask network stays fp32.  Runs in the
+                        per-image pass B.  Other values: hipErrorInvalidValue */
 } mcaq_morph_scale;
 int mcaq_morph(const mcaq_morph_scale* scales, int nscales, hipStream_t stream);
 /* mcaq_morph + mcaq_finalize in one launch: the channel min/max reduction
@@ -195,7 +202,25 @@ typedef struct {
   int ydtype;          /* element type of y: MCAQ_DTYPE_F32 only (the reference's result
                           type on fp16 / bf16 maps too: its fp32 tile mask promotes
                           the sum, quantization.py:732-738); else hipErrorInvalidValue */
+  int arith;           /* 0: fp32 arithmetic on every map (the default);
+                          MCAQ_ARITH_REFERENCE: the reference's arithmetic on an
+                          fp16 / bf16 map at inference with the batch's own
+                          statistics, every elementwise result rounded to the map's
+                          type (quantization.py:41-66, 409-434, 561-602, 729-746):
+                            rng = max(r(max - min), r(1e-8))   s = r(rng / (qmax - qmin))
+                            zp = clamp(r(qmin - r(min / s)), qmin, qmax)
+                            t = r(r(x / s) + zp)
+                            xq = r(r(clamp(rint(t), qmin, qmax) - zp) * s)
+                            y = (0 + xq) * m in fp32,
+                          and a non-finite xq at ANY width present in the scale's
+                          bit map makes y NaN there (the reference sums xq * 0 over
+                          those widths, all B images of the scale).  Needs dtype fp16 / bf16, stats_cover_x = 1,
+                          widths <= 8 bits and the tile-aligned geometry (as every
+                          half map); one value per launch; otherwise
+                          hipErrorNotSupported */
 } mcaq_quant_scale;
+#define MCAQ_ARITH_FP32 0
+#define MCAQ_ARITH_REFERENCE 1
 int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream);
 
 /* mcaq_morph_finalize with a choice of passes: bit 0 = pass A (the per-image

@@ -9,8 +9,9 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmcaq_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # MCAQ_DTYPE_*
+ARITH_FP32, ARITH_REFERENCE = 0, 1            # MCAQ_ARITH_* (mcaq_quant_scale.arith)
 MAX_SEGMENTS = 9   # MCAQ_MAX_SEGMENTS: segments (hook scale x batch) per launch
 
 P = ctypes.c_void_p
@@ -36,14 +37,14 @@ class MorphScale(ctypes.Structure):
                 ("B", I), ("H", I), ("W", I), ("Hc", I), ("Wc", I), ("tile", I), ("ht", I), ("wt", I),
                 ("batch_offset", I), ("batch_total", I), ("flags", I), ("hyst_iters", I),
                 ("temperature", Fl), ("min_bits", Fl), ("max_bits", Fl), ("block_begin", I),
-                ("softmax_threads", I), ("pwork", P)]
+                ("softmax_threads", I), ("pwork", P), ("smask_arith", I)]
 
 
 class QuantScale(ctypes.Structure):
     _fields_ = [("x", P), ("y", P), ("bits", P), ("m", P), ("mt", P), ("xmin", P), ("xmax", P),
                 ("B", I), ("C", I), ("H", I), ("W", I), ("ht", I), ("wt", I),
                 ("bits_lo", I), ("nbits", I), ("compat_tile_h", I), ("compat_tile_w", I), ("unit_begin", I),
-                ("stats_cover_x", I), ("neg_min", I), ("dtype", I), ("ydtype", I)]
+                ("stats_cover_x", I), ("neg_min", I), ("dtype", I), ("ydtype", I), ("arith", I)]
 
 
 class QatScale(ctypes.Structure):

@@ -34,6 +34,7 @@ the morph kernel, as in the reference).
 """
 import ctypes
 import functools
+import types
 from typing import Optional
 
 import torch
@@ -287,7 +288,18 @@ def _run_stats(x, gray=None, absmean=None, pmin=None, pmax=None, Hc=None, Wc=Non
     s.x, s.gray, s.absmean, s.pmin, s.pmax = _p(x), _p(gray), _p(absmean), _p(pmin), _p(pmax)
     s.B, s.C, s.H, s.W = B, C, H, W
     s.Hc, s.Wc = (H if Hc is None else Hc), (W if Wc is None else Wc)
+    s.dtype = _ABI_DTYPES[x.dtype]      # fp16 / bf16 maps widen exactly in pass 1
     abi.check(abi.lib().mcaq_stats(ctypes.byref(s), 1, _stream()), "mcaq_stats")
+
+
+_ABI_DTYPES = {torch.float32: abi.DTYPE_F32, torch.float16: abi.DTYPE_F16, torch.bfloat16: abi.DTYPE_BF16}
+HALF_ARITHMETIC = ("fp32", "reference")
+
+
+def _check_half_arithmetic(mode):
+    if mode not in HALF_ARITHMETIC:
+        raise ValueError("half_arithmetic must be one of %s, got %r" % (HALF_ARITHMETIC, mode))
+    return mode
 
 
 # Pass-1 sharing inside one hook call (train mode): the analyzer's pass 1
@@ -794,7 +806,10 @@ class LearnedSoftMask(nn.Module):
     def blob(self):
         return self._blob.get(list(self.net.parameters()), lambda: _pack_softmask(self.net))
 
-    def _run(self, bit_map, x, absmean, plane):
+    def _run(self, bit_map, x, absmean, plane, arith_dtype=None):
+        """arith_dtype: torch.float16 / torch.bfloat16 = the side information in
+        the reference's arithmetic on a map of that type
+        (mcaq_morph_scale.smask_arith); None: fp32."""
         _need_cuda(bit_map, "bit_map")
         _need_cuda(x, "x")
         B, C, H, W = x.shape
@@ -813,11 +828,22 @@ class LearnedSoftMask(nn.Module):
         ptrs = dict(absmean=absmean, bits_in=bits, smask=self.blob())
         ptrs["m_out" if plane else "mt_out"] = out
         s = _morph_struct(B, H, W, 4, ht, wt, abi.F_SOFTMASK, **ptrs)
+        if arith_dtype is not None:
+            s.smask_arith = _ABI_DTYPES[arith_dtype]
         abi.check(abi.lib().mcaq_morph(ctypes.byref(s), 1, _stream()), "mcaq_morph(soft mask)")
         return out
 
-    def forward(self, bit_map: torch.Tensor, x: torch.Tensor, absmean: Optional[torch.Tensor] = None):
+    def forward(self, bit_map: torch.Tensor, x: torch.Tensor, absmean: Optional[torch.Tensor] = None,
+                half_arithmetic: str = "fp32"):
+        """half_arithmetic="reference" (inference on an fp16 / bf16 map): the
+        side information in the map's own dtype, as the reference computes it
+        under autocast (fallback.soft_mask_act_reference_half)."""
+        ref = half_arithmetic == "reference" and x.dtype in fallback.HALF_DTYPES and not torch.is_grad_enabled()
         if not x.is_cuda:
+            if ref:
+                Ht, Wt = bit_map.shape[-2:]
+                return self._torch_forward(bit_map, None, act=fallback.soft_mask_act_reference_half(x, Ht, Wt),
+                                           size=x.shape[-2:])
             # pure-PyTorch path: per-pixel channel mean of |x| (no grad to x)
             if absmean is None:
                 absmean = x.detach().float().abs().mean(1)
@@ -829,16 +855,26 @@ class LearnedSoftMask(nn.Module):
                 absmean = torch.empty(B, H, W, device=x.device)
                 _run_stats(_f32c(x), absmean=absmean)
             return _SoftMaskFn.apply(bit_map, absmean, self, *self.net.parameters())
+        if ref:
+            # the half-rounded |x| channel mean by torch (one rounding of the
+            # fp32 sum / C, as on the CPU); tile mean, normalisation, network
+            # and the plane by the soft-mask stage in that arithmetic
+            absmean = x.detach().abs().mean(1).float().contiguous()
+            return self._run(bit_map, x, absmean, plane=True, arith_dtype=x.dtype)
         return self._run(bit_map, x, absmean, plane=True)
 
-    def _torch_forward(self, bit_map, absmean):
+    def _torch_forward(self, bit_map, absmean, act=None, size=None):
         """quantization.py:213-239 as torch ops (the backward recomputation);
-        absmean = x.abs().mean(1) from pass 1 (bit-identical to ATen's)."""
-        B, H, W = absmean.shape
+        absmean = x.abs().mean(1) from pass 1 (bit-identical to ATen's), or
+        act = the normalised tile activations themselves with size = (H, W)."""
         Ht, Wt = bit_map.shape[-2:]
-        with torch.no_grad():
-            act = F.adaptive_avg_pool2d(absmean.unsqueeze(1), (Ht, Wt))
-            act = act / (act.amax(dim=(2, 3), keepdim=True) + 1e-8)
+        if act is None:
+            B, H, W = absmean.shape
+            with torch.no_grad():
+                act = F.adaptive_avg_pool2d(absmean.unsqueeze(1), (Ht, Wt))
+                act = act / (act.amax(dim=(2, 3), keepdim=True) + 1e-8)
+        else:
+            H, W = size
         bits_norm = ((bit_map.unsqueeze(1).float() - 2.0) / 6.0).clamp(0.0, 1.0)
         logits = self.net(torch.cat([bits_norm, act.float()], dim=1))
         m = torch.softmax(logits, dim=1)[:, :1]
@@ -846,10 +882,10 @@ class LearnedSoftMask(nn.Module):
         p = self.kernel_size // 2
         return F.conv2d(F.pad(m, (p, p, p, p), mode="replicate"), self.smooth_kernel)
 
-    def tile_values(self, bit_map, x, absmean=None):
+    def tile_values(self, bit_map, x, absmean=None, arith_dtype=None):
         """m per tile before upsampling/smoothing (B, Ht, Wt); the quant pass
         turns it into m(p) on the fly."""
-        return self._run(bit_map, x, absmean, plane=False)
+        return self._run(bit_map, x, absmean, plane=False, arith_dtype=arith_dtype)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1448,11 +1484,24 @@ class _QATQuantFn(torch.autograd.Function):
 class SpatialAdaptiveQuantization(nn.Module):
     """quantization.py:242-754, inference: per-channel (batch, H, W) min/max (or
     frozen calibration stats) -> per-tile 2..8-bit quant/dequant x m(p).
-    One read of x for min/max + |x| mean, one read + one write for y."""
+    One read of x for min/max + |x| mean, one read + one write for y.
+
+    half_arithmetic: what an fp16 / bf16 map is quantized with at inference.
+    "fp32" (default): the map widens exactly and every operation is fp32.
+    "reference": the reference's own arithmetic under autocast - its quantizer
+    and the soft mask's side information run on the half tensors, every
+    elementwise result rounded to the map's dtype (fallback.
+    quantize_reference_half is the statement of it).  It applies to a half
+    map at inference with the batch's own statistics (per channel or per
+    tensor); frozen / EMA statistics are fp32 buffers, which promote the
+    reference's arithmetic to fp32, and keep the fp32 path.  A plain
+    attribute, not part of the state_dict."""
 
     def __init__(self, calibration_mode: str = "minmax", smooth_transitions: bool = True,
-                 per_channel: bool = True, learned_rounding: bool = False, momentum: float = 0.99):
+                 per_channel: bool = True, learned_rounding: bool = False, momentum: float = 0.99,
+                 half_arithmetic: str = "fp32"):
         super().__init__()
+        self.half_arithmetic = _check_half_arithmetic(half_arithmetic)
         if calibration_mode != "minmax":
             raise NotImplementedError("calibration_mode=%r: the hooks use 'minmax' "
                                       "(models/mcaq_yolo.py:466-470)" % calibration_mode)
@@ -1636,6 +1685,31 @@ class SpatialAdaptiveQuantization(nn.Module):
             return self.running_min.detach(), self.running_max.detach()
         return self._global_minmax(*self._batch_stats_torch(x.detach().float()))
 
+    def reference_half(self, x, training=False):
+        """True when this call runs the reference's half arithmetic: the mode is
+        selected, x is fp16 / bf16, the quantizer is in inference and the
+        statistics are the batch's own (not the frozen fp32 buffers)."""
+        if _check_half_arithmetic(self.half_arithmetic) != "reference" or x.dtype not in fallback.HALF_DTYPES:
+            return False
+        if training or self.training:
+            return False
+        return not (self.running_min is not None and self._frozen())
+
+    def _forward_reference_half(self, x, bit_map):
+        """Inference on a half map in the reference's arithmetic, as torch ops
+        on the tensor's device (fallback.quantize_reference_half): the CPU
+        path, and CUDA maps the tile-aligned kernel does not take.  On CUDA
+        the soft mask's tile mean, network and plane still come from the
+        soft-mask stage (LearnedSoftMask.forward)."""
+        if self.process_group is not None:
+            raise NotImplementedError("half_arithmetic='reference' with a process group on the module path")
+        with torch.no_grad():
+            xd = x.detach()
+            y = fallback.quantize_reference_half(xd, bit_map.detach(), self.per_channel)
+            if self.smooth_transitions and self.soft_mask is not None:
+                y = y * self.soft_mask(bit_map.detach(), xd, half_arithmetic="reference")
+        return y
+
     def _forward_torch(self, x, bit_map, training):
         """The pure-PyTorch quantizer (quantization.py:604-634, 681-746) for CPU
         tensors: one elementwise pass (fallback.quantize) at inference, the
@@ -1643,6 +1717,8 @@ class SpatialAdaptiveQuantization(nn.Module):
         B, C, H, W = x.shape
         if bit_map.dim() != 3 or bit_map.shape[0] != B:
             raise AssertionError(f"Batch size mismatch: {B} vs {bit_map.shape[0]}")
+        if self.reference_half(x, training):
+            return self._forward_reference_half(x, bit_map)
         if training:
             self.update_running_stats(x)
         xmin, xmax = self._minmax_for_quant(x)
@@ -1666,7 +1742,16 @@ class SpatialAdaptiveQuantization(nn.Module):
             return self._forward_train(x, bit_map)
         _need_cuda(x, "x")
         _need_cuda(bit_map, "bit_map")
-        xf = _f32c(x)
+        ref = self.reference_half(x, training)
+        if ref:
+            if bit_map.dim() != 3 or bit_map.shape[0] != x.shape[0]:
+                raise AssertionError(f"Batch size mismatch: {x.shape[0]} vs {bit_map.shape[0]}")
+            xf = x.detach().contiguous()
+            geom = types.SimpleNamespace(H=x.shape[2], W=x.shape[3], ht=bit_map.shape[1], wt=bit_map.shape[2])
+            if self.process_group is not None or not (_engine.half_native_ok(geom) and _engine.half_aligned(xf)):
+                return self._forward_reference_half(xf, bit_map)   # never the fp32 arithmetic
+        else:
+            xf = _f32c(x)
         B, C, H, W = xf.shape
         if bit_map.dim() != 3 or bit_map.shape[0] != B:
             raise AssertionError(f"Batch size mismatch: {B} vs {bit_map.shape[0]}")
@@ -1684,13 +1769,16 @@ class SpatialAdaptiveQuantization(nn.Module):
                 _run_stats(xf, absmean=absmean)
         else:
             xmin, xmax = self.batch_minmax(xf, absmean)
-        mt = self.soft_mask.tile_values(bits, xf, absmean=absmean) if want_m else None
-        y = torch.empty_like(xf)
+        mt = self.soft_mask.tile_values(bits, xf, absmean=absmean, arith_dtype=xf.dtype if ref else None) \
+            if want_m else None
+        y = torch.empty(xf.shape, device=xf.device)
         q = abi.QuantScale()
         q.x, q.y, q.bits, q.mt, q.xmin, q.xmax = _p(xf), _p(y), _p(bits), _p(mt), _p(xmin), _p(xmax)
         q.B, q.C, q.H, q.W, q.ht, q.wt = B, C, H, W, ht, wt
         q.bits_lo, q.nbits = 2, 7
         q.stats_cover_x = 0 if frozen else 1
+        q.dtype = _ABI_DTYPES[xf.dtype]
+        q.arith = abi.ARITH_REFERENCE if ref else abi.ARITH_FP32
         abi.check(abi.lib().mcaq_quant(ctypes.byref(q), 1, _stream()), "mcaq_quant")
         return y
 

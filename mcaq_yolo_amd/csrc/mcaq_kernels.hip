@@ -1435,6 +1435,238 @@ __global__ __launch_bounds__(256, 2) void mcaq_quant_tile_pipe_kernel(QuantArgs 
 }
 
 // ---------------------------------------------------------------------------
+// pass 2 in the reference's half arithmetic (mcaq_quant_scale.arith =
+// MCAQ_ARITH_REFERENCE): an fp16 / bf16 map at inference with the batch's own
+// statistics.  The reference runs QuantizationParameters and quantize_tensor
+// on the half tensors themselves (quantization.py:41-66, 409-434, 561-602), so
+// every elementwise result is rounded to the map's dtype, and sums x_q * mask
+// over the widths present in the bit map in fp32 (:729-738).  With r() =
+// round-to-nearest-even to the map's dtype:
+//   rng = max(r(max - min), r(1e-8))        s = r(rng / (qmax - qmin))
+//   zp  = clamp(r(qmin - r(min / s)), qmin, qmax)
+//   t   = r(r(x / s) + zp)
+//   xq  = r(r(clamp(rint(t), qmin, qmax) - zp) * s)        y = (0 + xq) * m
+// Each r(a op b) of two half values equals the native half operation (fp32
+// carries 24 >= 2 p + 2 bits: the double rounding is innocuous), so fp16 runs
+// its chain in v_*_f16 and bf16 in fp32 + one conversion per operation.  x / s
+// is div_by (mcaq_math.h): the correctly rounded fp32 quotient, whose rounding
+// to half is the half quotient.
+// Same unit geometry, loads and stores as quant_tile_unit.  The table carries
+// a flag per (width, channel) entry: set when the short chain is not provably
+// the literal one (s zero / non-finite / outside 1e-30..1e30, a NaN zero
+// point, |x| / s beyond 1e12, or (qmax - qmin) * s overflowing the dtype).  A
+// wave with a flagged entry among its 8 channels (at any width) takes the
+// literal chain: IEEE divisions, NaN-propagating clamps, and the reference's
+// sum over every width present in the scale's bit map - x_q * 0 of a
+// non-finite x_q at another width makes y NaN there.
+// ---------------------------------------------------------------------------
+template <typename T> struct RefHalf;
+template <> struct RefHalf<_Float16> {
+  static constexpr int DT = MCAQ_DTYPE_F16;
+  static __device__ __forceinline__ float r(float v) { return (float)(_Float16)v; }
+  // r(r(med3(rint(r(r(d) + zp)), qlo, qhi) - zp) * s) for finite operands
+  static __device__ __forceinline__ float chain(float d, float s, float zp, float qlo, float qhi) {
+    const _Float16 zh = (_Float16)zp, sh = (_Float16)s;
+    const _Float16 dh = (_Float16)d;
+    const _Float16 t = dh + zh;
+    const _Float16 q = __builtin_amdgcn_fmed3h(__builtin_rintf16(t), (_Float16)qlo, (_Float16)qhi);
+    const _Float16 u = q - zh;
+    const _Float16 xq = u * sh;
+    return (float)xq;
+  }
+};
+template <> struct RefHalf<Bf16> {
+  static constexpr int DT = MCAQ_DTYPE_BF16;
+  static __device__ __forceinline__ float r(float v) { return round_bf16(v); }
+  static __device__ __forceinline__ float rf(float v) {   // finite v
+    const uint32_t u = __float_as_uint(v);
+    return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
+  }
+  static __device__ __forceinline__ float chain(float d, float s, float zp, float qlo, float qhi) {
+    const float t = rf(rf(d) + zp);
+    const float q = __builtin_amdgcn_fmed3f(rintf(t), qlo, qhi);
+    return rf(rf(q - zp) * s);
+  }
+};
+
+// one [width][channel] table entry: (s, zp, RN(1 / s), flag)
+template <typename T>
+__device__ __forceinline__ float4 ref_qentry(float mn, float mx, int bits) {
+  typedef RefHalf<T> R;
+  const float qmin = (float)(-(1 << (bits - 1))), qmax = (float)((1 << (bits - 1)) - 1);
+  const float rng = fmaxp(R::r(mx - mn), R::r(1e-8f));          // torch.clamp(min=): NaN stays
+  const float s = R::r(rng / (qmax - qmin));
+  const float zp = clamp_nan(R::r(qmin - R::r(mn / s)), qmin, qmax);
+  const float big = fmaxf(fabsf(mn), fabsf(mx)) / s;
+  const bool safe = mn == mn && mx == mx && s >= 1e-30f && s <= 1e30f && big < 1e12f && zp == zp &&
+                    fabsf(R::r((qmax - qmin) * s)) <= 3.40282347e38f;
+  return make_float4(s, zp, 1.0f / s, safe ? 0.0f : 1.0f);
+}
+
+// the literal chain of one element at one width (any operand)
+template <typename T>
+__device__ __forceinline__ float ref_xq_any(float x, float4 e, float qlo, float qhi) {
+  typedef RefHalf<T> R;
+  const float t = R::r(R::r(x / e.x) + e.y);
+  const float q = clamp_nan(rintf(t), qlo, qhi);
+  return R::r(R::r(q - e.y) * e.x);
+}
+
+template <int kM, typename T>
+__device__ __forceinline__ void quant_tile_unit_ref(const QuantArgs& a, const int unit, float4* qt, float* mts,
+                                                    float4* mq4, int* qanyw) {
+  typedef RefHalf<T> R;
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  int si = 0;
+  while (si + 1 < a.nscales && unit >= a.s[si + 1].unit_begin) ++si;
+  const mcaq_quant_scale& S = a.s[si];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int H = S.H, W = S.W, HW = H * W;
+  const int sh = a.sh[si], sw = a.sw[si];
+  const int nsl = (S.C + QSLICE - 1) / QSLICE, upi = (HW + 255) >> 8;
+  const int lu = unit - S.unit_begin;
+  const int q1 = div_small(lu, nsl, a.rnsl[si]);
+  const int slice = lu - q1 * nsl;
+  const int b = div_small(q1, upi, a.rupi[si]);
+  const int chunk = q1 - b * upi;
+  const int c0 = slice * QSLICE;
+  const int nc = imin_(QSLICE, S.C - c0);
+  const int NB = S.nbits;
+  const int NTq = S.ht * S.wt;
+  // ---- 1. small operands (as quant_tile_unit)
+  const int tc = imin_(tid & (QSLICE - 1), nc - 1);
+  const float tmn0 = S.xmin[c0 + tc], tmx = S.xmax[c0 + tc];
+  const float tmn = S.neg_min ? -tmn0 : tmn0;
+  float mtv = 0.0f;
+  if (kM == QM_MT_LDS) mtv = S.mt[(size_t)b * NTq + imin_(tid, NTq - 1)];
+  const int q0 = chunk * 256 + lane * 4;
+  const bool pv = q0 < HW;
+  const int qa = pv ? q0 : 0;
+  const int h0 = div_small(qa, W, a.rw[si]), w0 = qa - h0 * W;
+  const float bv = S.bits[((size_t)b * S.ht + (h0 >> sh)) * S.wt + (w0 >> sw)];
+  // ---- 2. the x rows (8 x 8 B per lane), widened exactly
+  const int cw = wv * QCW;
+  const int ncw = imin_(QCW, nc - cw);
+  const size_t rowbase = ((size_t)b * S.C + c0 + imax_(imin_(cw, nc - 1), 0)) * HW;
+  const T* xb = reinterpret_cast<const T*>(S.x) + rowbase;
+  float* yb = S.y + rowbase;
+  f4v v[QCW];
+#pragma unroll
+  for (int c = 0; c < QCW; ++c) v[c] = ElemIO<T>::template ld4<true>(xb + (size_t)imin_(c, imax_(ncw - 1, 0)) * HW + qa);
+  // ---- 3. the table in the map's arithmetic, the flags, staged m(tile)
+  {
+    const int kq = imin_(tid >> 5, NB - 1);
+    const float4 e = ref_qentry<T>(tmn, tmx, S.bits_lo + kq);
+    qt[tid] = e;
+    int f = e.w != 0.0f ? 1 : 0;
+    f |= __shfl_xor(f, 32, 64);                 // the wave's two width rows
+    if (lane < QSLICE) qanyw[wv * QSLICE + lane] = f;
+  }
+  if (kM == QM_MT_LDS) {
+    if (tid < NTq) mts[tid] = mtv;
+    for (int i = tid + 256; i < NTq; i += 256) mts[i] = S.mt[(size_t)b * NTq + i];
+  }
+  const int kb = imin_(imax_((int)rintf(bv), S.bits_lo), S.bits_lo + NB - 1) - S.bits_lo;
+  const int hb = 1 << (S.bits_lo + kb - 1);
+  const float qlo = (float)(-hb), qhi = (float)(hb - 1);
+  __syncthreads();   // qt, qanyw, mts ready
+  // ---- 4. m(p) (as quant_tile_unit)
+  f4v m4 = {1.0f, 1.0f, 1.0f, 1.0f};
+  if (kM == QM_MT_LDS) {
+    const int w = w0 + wv;
+    int cs[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) cs[j] = imin_(imax_(w + j - 2, 0), W - 1) >> sw;
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const int rb = (imin_(imax_(h0 + i - 2, 0), H - 1) >> sh) * S.wt;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) acc = fmaf(bits_as_float(k_smooth5_bits[i * 5 + j]), mts[rb + cs[j]], acc);
+    }
+    reinterpret_cast<float*>(mq4)[lane * 4 + wv] = acc;
+    __syncthreads();
+    const float4 mm = mq4[lane];
+    m4 = f4v{mm.x, mm.y, mm.z, mm.w};
+  }
+  if (ncw <= 0) return;
+  // a flagged (width, channel) entry among this wave's channels: every width
+  // row of the table, since another width's x_q can reach y through x_q * 0
+  int fl = 0;
+  {
+    const int rl = lane & 31;
+    if ((rl & 7) < ncw) fl = qanyw[(rl >> 3) * QSLICE + cw + (rl & 7)];
+  }
+  const bool any_x = __builtin_amdgcn_ballot_w64(fl != 0) != 0;
+  const float4* qrow = qt + kb * QSLICE + cw;
+  if (!any_x) {
+#pragma unroll
+    for (int c = 0; c < QCW; ++c) {
+      if (c >= ncw) break;
+      const float4 e = qrow[c];
+      f4v o;
+      o.x = R::chain(div_by(v[c].x, e.x, e.z), e.x, e.y, qlo, qhi) + 0.0f;
+      o.y = R::chain(div_by(v[c].y, e.x, e.z), e.x, e.y, qlo, qhi) + 0.0f;
+      o.z = R::chain(div_by(v[c].z, e.x, e.z), e.x, e.y, qlo, qhi) + 0.0f;
+      o.w = R::chain(div_by(v[c].w, e.x, e.z), e.x, e.y, qlo, qhi) + 0.0f;
+      if (kM != QM_NONE) o = o * m4;
+      if (pv) ElemIO<float>::template st4<true>(yb + (size_t)c * HW + q0, o);
+    }
+    return;
+  }
+  // the widths present in the scale's bit map (torch.unique over all B images)
+  unsigned pm = 0;
+  for (int j = lane; j < S.B * NTq; j += 64)
+    pm |= 1u << (imin_(imax_((int)rintf(S.bits[j]), S.bits_lo), S.bits_lo + NB - 1) - S.bits_lo);
+  for (int o = 32; o > 0; o >>= 1) pm |= (unsigned)__shfl_xor((int)pm, o, 64);
+#pragma unroll 1
+  for (int c = 0; c < ncw; ++c) {
+    float xs[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
+#pragma unroll
+    for (int cc = 1; cc < QCW; ++cc)
+      if (cc == c) { xs[0] = v[cc].x; xs[1] = v[cc].y; xs[2] = v[cc].z; xs[3] = v[cc].w; }
+    float own[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    bool bad[4] = {false, false, false, false};
+#pragma unroll 1
+    for (int w = 0; w < NB; ++w) {
+      if (!((pm >> w) & 1u)) continue;
+      const float4 e = qt[w * QSLICE + cw + c];
+      const int hw = 1 << (S.bits_lo + w - 1);
+      const float wlo = (float)(-hw), whi = (float)(hw - 1);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float xq = ref_xq_any<T>(xs[k], e, wlo, whi);
+        if (w == kb) own[k] = xq;
+        else bad[k] = bad[k] || !(fabsf(xq) <= 3.40282347e38f);
+      }
+    }
+    f4v o;
+    o.x = bad[0] ? __builtin_nanf("") : own[0] + 0.0f;
+    o.y = bad[1] ? __builtin_nanf("") : own[1] + 0.0f;
+    o.z = bad[2] ? __builtin_nanf("") : own[2] + 0.0f;
+    o.w = bad[3] ? __builtin_nanf("") : own[3] + 0.0f;
+    if (kM != QM_NONE) o = o * m4;
+    if (pv) ElemIO<float>::template st4<true>(yb + (size_t)c * HW + q0, o);
+  }
+}
+
+template <int kM, typename T>
+__global__ MCAQ_QUANT_LB void mcaq_quant_tile_ref_kernel(QuantArgs a) {
+  __shared__ float4 qt[8 * QSLICE];           // [kb][c]: s, zp, 1/s, flag
+  __shared__ float mts[kM == QM_MT_LDS ? QMAXNT : 1];
+  __shared__ float4 mq4[64];
+  __shared__ int qanyw[4 * QSLICE];           // [wave][c]: a flagged entry in the wave's width rows
+#if MCAQ_STREAM_CAP > 0
+  for (int u = (int)blockIdx.x; u < a.units_total; u += (int)gridDim.x) {
+    quant_tile_unit_ref<kM, T>(a, u, qt, mts, mq4, qanyw);
+    __syncthreads();
+  }
+#else
+  quant_tile_unit_ref<kM, T>(a, (int)blockIdx.x, qt, mts, mq4, qanyw);
+#endif
+}
+
+// ---------------------------------------------------------------------------
 // extern "C" launchers
 // ---------------------------------------------------------------------------
 // Kernel timing (mcaq_time_next_launch): the next pass-1 / pass-2 launch of
@@ -1672,6 +1904,8 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
     if ((S.flags & F_PHI) && !S.tile_tmp) return (int)hipErrorInvalidValue;
     if ((S.flags & F_CMLP) && (!S.cmlp || (!(S.flags & F_PHI) && !S.phi_out))) return (int)hipErrorInvalidValue;
     if ((S.flags & F_SOFTMASK) && (!S.smask || !S.absmean)) return (int)hipErrorInvalidValue;
+    if (S.smask_arith != 0 && S.smask_arith != MCAQ_DTYPE_F16 && S.smask_arith != MCAQ_DTYPE_BF16)
+      return (int)hipErrorInvalidValue;
     S.block_begin = blocks;
     blocks += S.B;
     any_phi |= (S.flags & F_PHI) != 0;
@@ -1746,7 +1980,8 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
   bool tb = any_tiles != 0;
   for (int i = 0; i < nscales; ++i) {
     const int tf = a.s[i].flags & (F_PHI | F_CMLP | F_MAPPER | F_SOFTMASK);
-    if (tf && !tiles_batch_eligible(a.s[i])) tb = false;
+    // the soft mask's reference half arithmetic lives in the per-image pass B
+    if (tf && (!tiles_batch_eligible(a.s[i]) || a.s[i].smask_arith != 0)) tb = false;
   }
 #ifdef MCAQ_NO_TILES_BATCH
   tb = false;   // A/B: the per-image pass B
@@ -1908,8 +2143,16 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
         scales[i].ht < 1 || scales[i].wt < 1 || !scales[i].x || !scales[i].y || !scales[i].bits ||
         !scales[i].xmin || !scales[i].xmax || scales[i].dtype != scales[0].dtype ||
         scales[i].dtype < MCAQ_DTYPE_F32 || scales[i].dtype > MCAQ_DTYPE_BF16 ||
-        scales[i].ydtype != MCAQ_DTYPE_F32)
+        scales[i].ydtype != MCAQ_DTYPE_F32 || scales[i].arith < MCAQ_ARITH_FP32 ||
+        scales[i].arith > MCAQ_ARITH_REFERENCE)
       return (int)hipErrorInvalidValue;
+    // the reference's half arithmetic: a half map quantized with its own batch
+    // statistics at widths <= 8 bits (exact in fp16 and bf16), one mode per launch
+    if (scales[i].arith != scales[0].arith) return (int)hipErrorNotSupported;
+    if (scales[i].arith == MCAQ_ARITH_REFERENCE &&
+        (scales[i].dtype == MCAQ_DTYPE_F32 || !scales[i].stats_cover_x || scales[i].m ||
+         scales[i].bits_lo + scales[i].nbits - 1 > 8))
+      return (int)hipErrorNotSupported;
     units += scales[i].B * ((HW + 255) / 256) * ((scales[i].C + QSLICE - 1) / QSLICE);
   }
   a.nscales = nscales;
@@ -1976,6 +2219,15 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     // NT loads and stores)
     if (!tile_ok) return (int)hipErrorNotSupported;
     const dim3 g(MCAQ_STREAM_CAP > 0 ? imin_(units, MCAQ_STREAM_CAP * 256) : units);
+    if (scales[0].arith == MCAQ_ARITH_REFERENCE) {
+      switch ((kind == QM_NONE ? 0 : 1) + (dt == MCAQ_DTYPE_BF16 ? 2 : 0)) {
+        case 0: launch_k(mcaq_quant_tile_ref_kernel<QM_NONE, _Float16>, g, t, 0, stream, a); break;
+        case 1: launch_k(mcaq_quant_tile_ref_kernel<QM_MT_LDS, _Float16>, g, t, 0, stream, a); break;
+        case 2: launch_k(mcaq_quant_tile_ref_kernel<QM_NONE, Bf16>, g, t, 0, stream, a); break;
+        default: launch_k(mcaq_quant_tile_ref_kernel<QM_MT_LDS, Bf16>, g, t, 0, stream, a); break;
+      }
+      return (int)hipGetLastError();
+    }
     switch ((kind == QM_NONE ? 0 : 1) + (dt == MCAQ_DTYPE_BF16 ? 2 : 0)) {
       case 0: launch_k(mcaq_quant_tile_kernel<true, true, QM_NONE, _Float16, float>, g, t, 0, stream, a); break;
       case 1: launch_k(mcaq_quant_tile_kernel<true, true, QM_MT_LDS, _Float16, float>, g, t, 0, stream, a); break;

@@ -312,6 +312,41 @@ MCAQ_HD float quant_dequant_any(float x, const QParam& q) {
   return (r - q.zp) * q.scale;
 }
 
+// Reference half-precision arithmetic (an fp16 / bf16 map under autocast: the
+// reference's quantizer and soft-mask side information run in the map's own
+// dtype, every elementwise result rounded to it).  half_round(v, dt) is that
+// rounding of an fp32 value: round-to-nearest-even to fp16 (dt = 1,
+// MCAQ_DTYPE_F16; subnormals kept, overflow to inf) or bf16 (dt = 2) and
+// back to fp32; NaN stays NaN.  An fp32 +, -, *, / of two such values followed
+// by this rounding equals the native half operation (24 >= 2 p + 2 bits, so
+// the double rounding is innocuous).
+MCAQ_HD float round_f16(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (float)(_Float16)v;
+#else
+  if (!(fabsf(v) <= 3.40282347e38f)) return v;          // inf, NaN
+  const float a = fabsf(v);
+  float r;
+  if (a < 6.103515625e-05f) {
+    r = (a + 0.5f) - 0.5f;                               // ulp(0.5) = 2^-24: the fp16 subnormal grid
+  } else {
+    uint32_t u = float_as_bits(a);
+    u += 0xFFFu + ((u >> 13) & 1u);
+    u &= ~0x1FFFu;
+    r = bits_as_float(u);
+    if (r > 65504.0f) r = bits_as_float(0x7F800000u);
+  }
+  return v < 0.0f || (v == 0.0f && float_as_bits(v) != 0u) ? -r : r;
+#endif
+}
+MCAQ_HD float round_bf16(float v) {
+  if (v != v) return v;
+  uint32_t u = float_as_bits(v);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return bits_as_float(u & 0xFFFF0000u);
+}
+MCAQ_HD float half_round(float v, int dt) { return dt == 1 ? round_f16(v) : (dt == 2 ? round_bf16(v) : v); }
+
 // true when a channel with batch statistics [xmin, xmax] needs
 // quant_dequant_any (a NaN or +-inf in the channel, or huge magnitudes)
 MCAQ_HD bool stats_need_any(float xmin, float xmax) {

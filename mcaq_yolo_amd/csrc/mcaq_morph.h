@@ -1578,6 +1578,22 @@ MCAQ_HD float smask_act_tile(const float* am, int H, int W, int ht, int wt, floa
   return (s / (float)(hb - ha)) / (float)(wb - wa);
 }
 
+// The same in the reference's half arithmetic (mcaq_morph_scale.smask_arith =
+// dt: quantization.py:226-228 on an fp16 / bf16 map).  x.abs().mean(1) is the
+// fp32 channel sum divided by C, rounded ONCE to the map's dtype (ATen rounds
+// neither the channel sum nor the window sum before dividing): the absmean
+// plane of pass 1, rounded here.  adaptive_avg_pool2d accumulates those half
+// values in fp32 in the same row-major order and rounds the mean once.
+MCAQ_HD float smask_act_tile_ref(const float* am, int H, int W, int ht, int wt, float inv_wt, int t, int dt) {
+  const int i = div_small(t, wt, inv_wt), j = t - i * wt;
+  const int ha = (i * H) / ht, hb = ((i + 1) * H + ht - 1) / ht;
+  const int wa = (j * W) / wt, wb = ((j + 1) * W + wt - 1) / wt;
+  float s = 0.0f;
+  for (int h = ha; h < hb; ++h)
+    for (int w = wa; w < wb; ++w) s = s + half_round(am[h * W + w], dt);
+  return half_round((s / (float)(hb - ha)) / (float)(wb - wa), dt);
+}
+
 // xs: the workgroup's MLP activation scratch (MLP_SCRATCH_FLOATS per wave), device only
 // kSmo: a soft-mask-only launch (every scale F_SOFTMASK with bits_in and at
 // most one tile per thread of its image group; host-checked)
@@ -1796,21 +1812,26 @@ MCAQ_HD void morph_tiles(const Ctx& ctx, const MorphScale& S, int b, Shared& sh,
   if (S.flags & F_SOFTMASK) {
     const int H = S.H, W = S.W;
     const float* am = S.absmean + (size_t)b * H * W;
+    const int adt = S.smask_arith;   // 0, or the dtype the side information is rounded to
     float lmx = -3.402823466e38f;
     MFOR(t, NT) {
-      const float a = kSmo ? pre_a : smask_act_tile(am, H, W, ht, wt, inv_wt, t);
+      const float a = adt ? smask_act_tile_ref(am, H, W, ht, wt, inv_wt, t, adt)
+                          : (kSmo ? pre_a : smask_act_tile(am, H, W, ht, wt, inv_wt, t));
       tiles[t * TS + T_ACT] = a;
       lmx = fmaxp(lmx, a);          // torch.amax: a NaN activation makes the image's max NaN
     }
     const float amax = block_max(ctx, sh, lmx);
     MSTAMP(31);
-    const float den = amax + 1e-8f;
+    // reference half arithmetic: amax + 1e-8 and the quotient are half results
+    // (1e-8 itself rounds to 0 in fp16)
+    const float den = adt ? half_round(amax + half_round(1e-8f, adt), adt) : amax + 1e-8f;
     // the two conv input features, compact: f0 = bits feature, f1 = activation
     float* f0a = extra;
     float* f1a = extra + NT;
     MFOR(t, NT) {
       f0a[t] = clampf_((tiles[t * TS + T_BITS] - 2.0f) / 6.0f, 0.0f, 1.0f);
-      f1a[t] = tiles[t * TS + T_ACT] / den;
+      const float f1 = tiles[t * TS + T_ACT] / den;
+      f1a[t] = adt ? half_round(f1, adt) : f1;
     }
     MSYNC();
     MFOR(t, NT) {

@@ -216,7 +216,8 @@ class HookPlan:
     def prepare(self, feats, cmlp, mapper, smasks, temperature=1.0, mapper_kind="mlp", continuous=False,
                 normalize=False, minmax=None, batch_offset=0, batch_total=None, binarize_otsu=False,
                 contour_components=True, canny_legacy=False, min_bits=2.0, max_bits=8.0, quantize=True, hysteresis_iters=8,
-                per_tensor=False, softmax_threads=None, m_plane=False, shared_stats=False):
+                per_tensor=False, softmax_threads=None, m_plane=False, shared_stats=False,
+                half_arithmetic="fp32"):
         """Validate inputs and build the launch descriptors (pointers are baked
         in: the tensors must stay alive and in place until the last launch).
         A call with the same blobs, buffers and options as the previous one
@@ -233,6 +234,11 @@ class HookPlan:
         shared_stats: the statistics of a batch-sharded run - the finalize
         writes [-min | max] into `mm` and pass 2 reads the min negated, so
         launch(process_group=...) combines them with ONE in-place all-reduce.
+        half_arithmetic: "reference" runs pass 2 and the soft mask's side
+        information of fp16 / bf16 maps in the reference's own arithmetic,
+        every elementwise result rounded to the map's dtype (mcaq_quant_scale.
+        arith, mcaq_morph_scale.smask_arith); it needs half maps and the
+        batch's own statistics (minmax=None).  Default "fp32".
         With batches > 1, feats is one list per batch; smasks and minmax are
         per scale and shared by the batches."""
         ns = len(self.scale_geoms)
@@ -268,6 +274,12 @@ class HookPlan:
                 raise ValueError("%s feature maps need the tile-aligned quantizer (engine.half_native_ok)" % dtype)
             if not all(half_aligned(f) for f in feats):
                 raise ValueError("%s feature maps need a 16-byte aligned base (engine.half_aligned)" % dtype)
+        if half_arithmetic not in ("fp32", "reference"):
+            raise ValueError("half_arithmetic must be 'fp32' or 'reference', got %r" % (half_arithmetic,))
+        ref = half_arithmetic == "reference"
+        if ref and (dtype == torch.float32 or (minmax is not None and any(e is not None for e in minmax))):
+            raise ValueError("half_arithmetic='reference' takes fp16 / bf16 maps quantized with the batch's own "
+                             "statistics (frozen statistics promote the reference's arithmetic to fp32)")
         # descriptor reuse: an eager hook calls prepare once per forward with
         # new x / output tensors and otherwise the same blobs, buffers and
         # options; then only those pointers are patched into the structs
@@ -276,7 +288,7 @@ class HookPlan:
             int(batch_offset), batch_total, bool(binarize_otsu), bool(contour_components), bool(canny_legacy),
             float(min_bits), float(max_bits), bool(quantize), int(hysteresis_iters), bool(per_tensor),
             int(softmax_threads) if softmax_threads else torch.get_num_threads(), bool(m_plane),
-            bool(shared_stats), str(dtype)))
+            bool(shared_stats), str(dtype), half_arithmetic))
         if sig is not None and sig == getattr(self, "_sig", None):
             self._rebind(feats)
             self._keep = (list(feats), cmlp, mapper, list(smasks), minmax)
@@ -358,6 +370,9 @@ class HookPlan:
             s.hyst_iters = hysteresis_iters
             s.softmax_threads = int(softmax_threads) if softmax_threads else torch.get_num_threads()
             s.temperature, s.min_bits, s.max_bits = T, float(min_bits), float(max_bits)
+            if ref and with_mask[i] and quantize:
+                s.flags |= abi.F_TILES_IMAGE       # the per-image pass B holds this arithmetic
+                s.smask_arith = _DTYPES[dtype]
         self._mo = mo
         # ---- pass 2
         if quantize:
@@ -379,6 +394,7 @@ class HookPlan:
                 s.neg_min = 1 if self._neg else 0
                 s.dtype = _DTYPES[dtype]
                 s.ydtype = abi.DTYPE_F32      # the reference's result type on every map
+                s.arith = abi.ARITH_REFERENCE if ref else abi.ARITH_FP32
             self._qs = qs
         self._n = n
         self._sig = sig

@@ -410,6 +410,55 @@ def quantize(x, bits, xmin, xmax, m=None, lo=2, hi=8):
     return y if m is None else y * m
 
 
+HALF_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def quantize_reference_half(x, bit_map, per_channel=True, xmin=None, xmax=None):
+    """The reference's inference quantizer on an fp16 / bf16 map, as it runs
+    under autocast (half_arithmetic="reference"): the same torch ops on the
+    half tensors themselves, in the reference's order, so every elementwise
+    result is rounded to the map's dtype (quantization.py:41-66 scale / zero
+    point, :409-434 the batch's own min / max, :561-602 quantize_tensor,
+    :729-738 the per-width loop).  The fp32 nearest tile mask promotes the sum,
+    so the result is fp32; x_q * 0 of a non-finite x_q at another width
+    present in the bit map makes y NaN there, as in the reference.  This
+    function is the ground truth of the mode's semantics: the HIP kernel
+    (mcaq_quant_tile_ref_kernel) is tested against it bit for bit.
+    xmin / xmax: the batch statistics when they come from elsewhere (a
+    process group's all-reduce), in the map's dtype and the reference's
+    keepdim shape; default: computed here."""
+    if x.dtype not in HALF_DTYPES:
+        raise TypeError("quantize_reference_half takes an fp16 / bf16 map, got %s" % x.dtype)
+    B, C, H, W = x.shape
+    if xmin is None:
+        if per_channel:
+            dims = [0] + list(range(2, x.dim()))
+            xmin, xmax = x.amin(dim=dims, keepdim=True), x.amax(dim=dims, keepdim=True)
+        else:
+            xmin, xmax = x.min(), x.max()
+    y = torch.zeros_like(x)
+    for v in torch.unique(bit_map):
+        b = int(round(float(v.item())))
+        qmin, qmax = -(2 ** (b - 1)), 2 ** (b - 1) - 1
+        scale = torch.clamp(xmax - xmin, min=1e-8) / (qmax - qmin)
+        zp = torch.clamp(qmin - xmin / scale, qmin, qmax)
+        xq = (torch.clamp(torch.round(x / scale + zp), qmin, qmax) - zp) * scale
+        tile = (bit_map == v).float().unsqueeze(1)
+        y = y + xq * F.interpolate(tile, size=(H, W), mode="nearest")
+    return y
+
+
+def soft_mask_act_reference_half(x, Ht, Wt):
+    """The soft mask's side information on an fp16 / bf16 map in the
+    reference's arithmetic (quantization.py:226-228): (B, 1, Ht, Wt) in the
+    map's dtype.  ATen rounds x.abs().mean(1) once (fp32 sum / C -> half) and
+    the pooled mean once; amax + 1e-8 and the quotient are half operations."""
+    if x.dtype not in HALF_DTYPES:
+        raise TypeError("soft_mask_act_reference_half takes an fp16 / bf16 map, got %s" % x.dtype)
+    act = F.adaptive_avg_pool2d(x.detach().abs().mean(1, keepdim=True), (Ht, Wt))
+    return act / (act.amax(dim=(2, 3), keepdim=True) + 1e-8)
+
+
 def spatial_quantize(x, bit_map, min_vals, max_vals, tile_h, tile_w, mask=None):
     """mcaq_cuda_ops.spatial_quantize semantics on CPU tensors: bits
     clamp(rint(b), 2, 8) of tile min(h // tile_h, Ht - 1) (mcaq_kernel.cu:

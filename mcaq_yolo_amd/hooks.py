@@ -43,8 +43,14 @@ CONCURRENT_TRAIN_SCALES = True
 
 class MCAQHooks(nn.Module):
     def __init__(self, grid_size=8, min_bits=2, max_bits=8, bit_mapping="mlp", normalize_complexity=False,
-                 device="cuda", indices=DEFAULT_INDICES):
+                 device="cuda", indices=DEFAULT_INDICES, half_arithmetic="fp32"):
+        """half_arithmetic: "fp32" (default) quantizes an fp16 / bf16 map in
+        fp32 on the exactly widened values; "reference" reproduces the
+        reference's own arithmetic under autocast, every elementwise result
+        rounded to the map's dtype (core.SpatialAdaptiveQuantization).  The
+        bit maps are the same in both modes.  Not part of the state_dict."""
         super().__init__()
+        self.half_arithmetic = core._check_half_arithmetic(half_arithmetic)
         self.complexity_analyzer = MorphologicalComplexityAnalyzer(grid_size=grid_size, device=device)
         if bit_mapping == "mlp":
             self.bit_mapper = ComplexityToBitMappingNetwork(min_bits=min_bits, max_bits=max_bits)
@@ -58,7 +64,8 @@ class MCAQHooks(nn.Module):
         self.backbone_out_indices = list(indices)
         for idx in self.backbone_out_indices:
             self.quantizers[str(idx)] = SpatialAdaptiveQuantization(calibration_mode="minmax",
-                                                                    smooth_transitions=True, per_channel=True)
+                                                                    smooth_transitions=True, per_channel=True,
+                                                                    half_arithmetic=half_arithmetic)
         self._mcaq_state = {"active": False}
         # batch-sharded inference (one process per GPU): the per-channel batch
         # min/max is made global by one all-reduce per hook, and the fractal
@@ -240,9 +247,21 @@ class MCAQHooks(nn.Module):
         half = feat.dtype in (torch.float16, torch.bfloat16)
         x = feat.contiguous() if half else feat.float().contiguous()
         plan = self._plan(x)
+        # the reference's half arithmetic (half_arithmetic="reference"): pass 2
+        # and the soft mask's side information in the map's dtype where the
+        # kernel takes the map; a map it does not take gets its bits from the
+        # plan (fp32 analysis, as always) and is quantized by the torch
+        # restatement on the device - never by the fp32 arithmetic
+        ref = half and quantize and quantizer.reference_half(feat) and not state.get("calibrating", False)
+        ref_torch = None
         if half and not (engine.half_aligned(x) and
                          all(engine.half_native_ok(g, self.bit_mapper.min_bits, self.bit_mapper.max_bits)
                              for g in plan.geoms)):
+            if ref:
+                if self.process_group is not None:
+                    raise NotImplementedError("half_arithmetic='reference' on a batch-sharded map the "
+                                              "tile-aligned kernel does not take (engine.half_native_ok)")
+                ref_torch, ref, quantize = x, False, False
             x = x.float()
         if state.get("calibrating", False) and quantize:
             quantizer.update_running_stats(x.float())
@@ -261,7 +280,11 @@ class MCAQHooks(nn.Module):
                  binarize_otsu=an.binarize_impl == "otsu", contour_components=an.contour_components,
                  canny_legacy=an.canny_impl == "legacy", min_bits=self.bit_mapper.min_bits, max_bits=self.bit_mapper.max_bits, quantize=quantize,
                  per_tensor=not quantizer.per_channel, softmax_threads=self.softmax_threads, process_group=self.process_group if minmax is None else None,
-                 batch_offset=self.batch_offset, batch_total=self.batch_total)
+                 batch_offset=self.batch_offset, batch_total=self.batch_total,
+                 half_arithmetic="reference" if ref else "fp32")
+        if ref_torch is not None:
+            quantize = True
+            b["y"] = quantizer._forward_reference_half(ref_torch, b["bits"])
         feat_q = b["y"] if quantize else feat
         state.setdefault("aux", []).append({"layer": layer_idx, "complexity": b["complexity"],
                                             "bit_map": b["bits"], "features_q": feat_q})
