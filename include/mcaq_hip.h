@@ -44,8 +44,9 @@ typedef void* hipEvent_t;
 extern "C" {
 #endif
 
-#define MCAQ_ABI_VERSION 29
-/* feature-map element types (mcaq_stats_scale.dtype, mcaq_quant_scale.dtype) */
+#define MCAQ_ABI_VERSION 30
+/* feature-map element types (mcaq_stats_scale.dtype, mcaq_quant_scale.dtype,
+ * mcaq_qat_scale.dtype) */
 #define MCAQ_DTYPE_F32 0
 #define MCAQ_DTYPE_F16 1
 #define MCAQ_DTYPE_BF16 2
@@ -248,12 +249,21 @@ int mcaq_time_launch(int skip, hipEvent_t start, hipEvent_t stop);
  *           quantization.py:94-118); gm_out(p) = sum_c g xq (NULL: skip);
  *           gb(t) = sum over tile t's pixels of sum_c (gm Q_hi - gm Q_lo)
  *           (NULL: skip).  work: mcaq_qat_work_floats(B,C,H,W) floats of
- *           device scratch (per-32-channel-slice partials of both sums). */
+ *           device scratch (per-32-channel-slice partials of both sums).
+ * x and gx have the element type `dtype` (the map an autocast region hands
+ * the hook and its gradient); every other array is fp32.  An fp16 / bf16 x
+ * widens exactly and the arithmetic is fp32: y, gm and gb are bit for bit
+ * those of the fp32 call on the widened x, and gx is that call's gx rounded
+ * once to `dtype` (nearest even, overflow to inf, NaN stays NaN).  Rows are
+ * read and written 4 elements a lane when H*W % 4 == 0 and every base is
+ * aligned to its own 4 elements (16 bytes: g, y, an fp32 x / gx; 8 bytes: an
+ * fp16 / bf16 x / gx); any other shape or alignment takes the element-wise
+ * kernel of the same type - the library never upcasts. */
 typedef struct {
-  const float* x;      /* (B, C, H, W) */
-  const float* g;      /* (B, C, H, W) upstream gradient (backward) */
-  float* y;            /* (B, C, H, W) forward output */
-  float* gx;           /* (B, C, H, W) backward output */
+  const float* x;      /* (B, C, H, W), element type `dtype` */
+  const float* g;      /* (B, C, H, W) upstream gradient (backward), fp32 */
+  float* y;            /* (B, C, H, W) forward output, fp32 */
+  float* gx;           /* (B, C, H, W) backward output, element type `dtype` */
   float* gm;           /* (B, H, W) grad of m, or NULL */
   float* gb;           /* (B, ht, wt) grad of the bit map, or NULL */
   float* work;         /* backward scratch */
@@ -268,6 +278,9 @@ typedef struct {
                           finish a (image, tile row) band folds that band's
                           partials into gm / gb inside the same launch;
                           NULL: a separate fold kernel does it */
+  int dtype;           /* element type of x and gx: MCAQ_DTYPE_F32 (0) / _F16 / _BF16,
+                          one per launch; another value, or scales of different
+                          types in one launch: hipErrorInvalidValue, nothing launched */
 } mcaq_qat_scale;
 int mcaq_qat_forward(const mcaq_qat_scale* scales, int nscales, hipStream_t stream);
 int mcaq_qat_backward(const mcaq_qat_scale* scales, int nscales, hipStream_t stream);
@@ -589,7 +602,7 @@ typedef struct {
 int mcaq_pack(const mcaq_pack_seg* segs, int nseg, float* out, int total, hipStream_t stream);
 /* mcaq_stats(scales, nscales) with mcaq_pack(segs, nseg, out, total) riding
  * on the same launch as extra workgroups (the train step re-packs its blobs
- * beside pass 1, which reads none of them). */
+ * beside pass 1, which reads none of them); every element type of mcaq_stats. */
 int mcaq_stats_pack(const mcaq_stats_scale* scales, int nscales, const mcaq_pack_seg* segs, int nseg, float* out,
                     int total, hipStream_t stream);
 

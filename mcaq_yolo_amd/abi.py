@@ -9,7 +9,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmcaq_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # MCAQ_DTYPE_*
 ARITH_FP32, ARITH_REFERENCE = 0, 1            # MCAQ_ARITH_* (mcaq_quant_scale.arith)
 MAX_SEGMENTS = 9   # MCAQ_MAX_SEGMENTS: segments (hook scale x batch) per launch
@@ -51,7 +51,7 @@ class QatScale(ctypes.Structure):
     _fields_ = [("x", P), ("g", P), ("y", P), ("gx", P), ("gm", P), ("gb", P), ("work", P),
                 ("bits", P), ("m", P), ("xmin", P), ("xmax", P),
                 ("B", I), ("C", I), ("H", I), ("W", I), ("ht", I), ("wt", I),
-                ("unit_begin", I), ("block_begin", I), ("arrive", P)]
+                ("unit_begin", I), ("block_begin", I), ("arrive", P), ("dtype", I)]
 
 
 class MapperParams(ctypes.Structure):

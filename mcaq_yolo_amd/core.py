@@ -296,6 +296,26 @@ _ABI_DTYPES = {torch.float32: abi.DTYPE_F32, torch.float16: abi.DTYPE_F16, torch
 HALF_ARITHMETIC = ("fp32", "reference")
 
 
+def half_native(*xs):
+    """True when the train-mode kernels read these maps as they are (pass 1
+    and the QAT quantizer take fp16 / bf16 elements, mcaq_stats_scale.dtype /
+    mcaq_qat_scale.dtype): CUDA fp16 / bf16 maps of ONE dtype (a launch has
+    one element type), contiguous, bases 8-byte aligned (a lane's four
+    elements), and train_step.HALF_NATIVE set (read at call time).  Anything
+    else - fp32 maps among them - keeps the x.float() route."""
+    from . import train_step
+    if not (train_step.HALF_NATIVE and xs) or len({x.dtype for x in xs if torch.is_tensor(x)}) != 1:
+        return False
+    return all(torch.is_tensor(x) and x.is_cuda and x.dtype in fallback.HALF_DTYPES and x.is_contiguous() and
+               x.data_ptr() % 8 == 0 for x in xs)
+
+
+def _train_map(x):
+    """The map the train-mode kernels read: x itself when half_native, else
+    its contiguous fp32 copy (no copy for a contiguous fp32 map)."""
+    return x.detach() if half_native(x) else _f32c(x)
+
+
 def _check_half_arithmetic(mode):
     if mode not in HALF_ARITHMETIC:
         raise ValueError("half_arithmetic must be one of %s, got %r" % (HALF_ARITHMETIC, mode))
@@ -418,7 +438,8 @@ class MorphologicalComplexityAnalyzer(nn.Module):
         _need_cuda(features, "features")
         if features.dim() != 4:
             raise ValueError("features must be (B, C, H, W)")
-        x = features.float().contiguous()
+        # train mode: an fp16 / bf16 map goes to pass 1 as it is (half_native)
+        x = features.detach() if (self.training and half_native(features)) else features.float().contiguous()
         B, C, H, W = x.shape
         T = tile_size(H, self.grid_size)
         ht, wt = H // T, W // T
@@ -817,7 +838,7 @@ class LearnedSoftMask(nn.Module):
         _, ht, wt = bits.shape
         if absmean is None:
             absmean = torch.empty(B, H, W, device=x.device)
-            _run_stats(_f32c(x), absmean=absmean)
+            _run_stats(_train_map(x), absmean=absmean)
         if 4 * ht > H or 4 * wt > W:
             # the launcher's geometry check wants >= 4 pixels per tile (every
             # hook tile grid has them: tile = pow2floor(max(4, H // grid)))
@@ -853,7 +874,7 @@ class LearnedSoftMask(nn.Module):
             if absmean is None:
                 B, C, H, W = x.shape
                 absmean = torch.empty(B, H, W, device=x.device)
-                _run_stats(_f32c(x), absmean=absmean)
+                _run_stats(_train_map(x), absmean=absmean)
             return _SoftMaskFn.apply(bit_map, absmean, self, *self.net.parameters())
         if ref:
             # the half-rounded |x| channel mean by torch (one rounding of the
@@ -1400,18 +1421,22 @@ def _smask_backward_fused(ctx, mod, bit_map, absmean, gm, params):
 
 
 def _qat_struct(x, bits, m, xmin, xmax):
+    """x: contiguous fp32, fp16 or bf16 (mcaq_qat_scale.dtype: the type of x and
+    of grad_x); every other tensor fp32."""
     B, C, H, W = x.shape
     q = abi.QatScale()
     q.x, q.bits, q.m, q.xmin, q.xmax = _p(x), _p(bits), _p(m), _p(xmin), _p(xmax)
     q.B, q.C, q.H, q.W = B, C, H, W
     q.ht, q.wt = bits.shape[-2], bits.shape[-1]
+    q.dtype = _ABI_DTYPES[x.dtype]
     return q
 
 
 def qat_quantize(x, bits, m, xmin, xmax):
     """Fractional-bit QAT forward (quantization.py:699-727, 733-737) on the HIP
-    kernel: y = ((1-f) Q_floor(b) + f Q_floor(b)+1)(x) * m.  No autograd."""
-    y = torch.empty_like(x)
+    kernel: y = ((1-f) Q_floor(b) + f Q_floor(b)+1)(x) * m.  No autograd.
+    x is fp32, or fp16 / bf16 read as it is (widened exactly); y is fp32."""
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     q = _qat_struct(x, bits, m, xmin, xmax)
     q.y = _p(y)
     abi.check(abi.lib().mcaq_qat_forward(ctypes.byref(q), 1, _stream()), "mcaq_qat_forward")
@@ -1448,10 +1473,11 @@ def _arrive_counters(B, device):
 
 def qat_quantize_backward(g, x, bits, m, xmin, xmax, want_gm=True, want_gb=True):
     """Straight-through backward (quantization.py:94-118 + the autograd graph of
-    :699-737): (grad_x, grad_bits (B,ht,wt) or None, grad_m (B,H,W) or None)."""
+    :699-737): (grad_x, grad_bits (B,ht,wt) or None, grad_m (B,H,W) or None).
+    g is fp32; grad_x has x's dtype (fp16 / bf16: the fp32 value rounded once)."""
     B, C, H, W = x.shape
     L = abi.lib()
-    gx = torch.empty_like(x)
+    gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     gm = torch.empty(B, H, W, device=x.device) if (want_gm and m is not None) else None
     gb = torch.empty(bits.shape, device=x.device) if want_gb else None
     work = torch.empty(L.mcaq_qat_work_floats(B, C, H, W), device=x.device)
@@ -1466,7 +1492,9 @@ def qat_quantize_backward(g, x, bits, m, xmin, xmax, want_gm=True, want_gb=True)
 class _QATQuantFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bit_map, m, xmin, xmax):
-        xf, bits = _f32c(x), _f32c(bit_map)
+        # a half map (half_native) is read, saved and differentiated as it is:
+        # no fp32 copy lives until the backward, grad_x comes back in its dtype
+        xf, bits = _train_map(x), _f32c(bit_map)
         mf = None if m is None else _f32c(m)
         ctx.save_for_backward(xf, bits, mf, xmin, xmax)
         return qat_quantize(xf, bits, mf, xmin, xmax)
@@ -1593,7 +1621,7 @@ class SpatialAdaptiveQuantization(nn.Module):
         if not x.is_cuda:
             return self._update_running_stats_torch(x)
         _need_cuda(x, "x")
-        xf = _f32c(x)
+        xf = _train_map(x)
         xmin, xmax = _channel_minmax(xf, absmean, partials)
         if self.process_group is not None:
             # data-parallel QAT: the EMA sees the global batch's min/max (one
@@ -1654,7 +1682,7 @@ class SpatialAdaptiveQuantization(nn.Module):
         if bit_map.dim() != 3 or bit_map.shape[0] != B:
             raise AssertionError(f"Batch size mismatch: {B} vs {bit_map.shape[0]}")
         want_m = self.smooth_transitions and self.soft_mask is not None
-        xf = _f32c(x)
+        xf = _train_map(x)      # the analyzer's pass 1 read the same tensor (_pass1_lookup)
         hit = _pass1_lookup(xf)
         absmean = (hit["absmean"] if hit is not None else torch.empty(B, H, W, device=x.device)) if want_m else None
         frozen = self._frozen()

@@ -147,11 +147,24 @@ __device__ __forceinline__ void wave_minmax16(float (&mn)[ST_CG], float (&mx)[ST
 // arithmetic stays fp32: the analyzer's gray / |x| sums are those of
 // x.float(), morphology.py:834-837).  y is always fp32, the reference's
 // result type on a half map (quantization.py:736-738: the fp32 tile mask
-// promotes the sum), so only fp32 has a store.
+// promotes the sum), so pass 2 stores fp32 only.  The half stores (st, st4)
+// serve the QAT backward's grad_x, which has the map's type: ONE
+// round-to-nearest-even of the fp32 value (fp16: the hardware conversion,
+// overflow to inf, subnormals kept; bf16: bf16_rne), four elements packed
+// into one 8-byte store.
 typedef float mcaq_f4v __attribute__((ext_vector_type(4)));
 typedef _Float16 mcaq_h4v __attribute__((ext_vector_type(4)));
 typedef unsigned short mcaq_u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float bf16_f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
+// fp32 -> bf16, round to nearest even on the bit pattern (the statement of
+// c10::detail::round_to_nearest_even): the carry of the rounding add runs into
+// the exponent, so values past the largest finite bf16 become inf and +-inf
+// stay; NaN stays NaN (quiet bit set, payload not kept)
+__device__ __forceinline__ unsigned short bf16_rne(float f) {
+  const unsigned u = __float_as_uint(f);
+  const unsigned r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+  return (unsigned short)(f != f ? ((u >> 16) | 0x40u) : r);
+}
 // The nontemporal choice is a template argument: a runtime `nt ? ntload(p)
 // : *p` lets LLVM merge the two loads of one address and drop the
 // nontemporal bit (round 6: pass 1's x loads lost `nt` that way, -10 % on
@@ -166,8 +179,14 @@ __device__ __forceinline__ void st_v(V* p, V v) {
   if constexpr (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
+// pk4 / ldp / ldp4 / widen: four elements as loaded (an fp16 / bf16 quad is
+// two registers until it is widened at its use)
 template <typename T> struct ElemIO;
 template <> struct ElemIO<float> {
+  typedef mcaq_f4v pk4;
+  static __device__ __forceinline__ float ldp(const float* p) { return *p; }
+  template <bool NT> static __device__ __forceinline__ pk4 ldp4(const float* p) { return ld4<NT>(p); }
+  static __device__ __forceinline__ mcaq_f4v widen(pk4 v) { return v; }
   static __device__ __forceinline__ float ld(const float* p) { return *p; }
   template <bool NT> static __device__ __forceinline__ mcaq_f4v ld4(const float* p) {
     return ld_v<NT>(reinterpret_cast<const mcaq_f4v*>(p));
@@ -176,22 +195,45 @@ template <> struct ElemIO<float> {
   template <bool NT> static __device__ __forceinline__ void st4(float* p, mcaq_f4v v) {
     st_v<NT>(reinterpret_cast<mcaq_f4v*>(p), v);
   }
+  static __device__ __forceinline__ void st(float* p, float v) { *p = v; }
 };
 template <> struct ElemIO<_Float16> {
+  typedef mcaq_h4v pk4;
+  static __device__ __forceinline__ _Float16 ldp(const _Float16* p) { return *p; }
+  template <bool NT> static __device__ __forceinline__ pk4 ldp4(const _Float16* p) {
+    return ld_v<NT>(reinterpret_cast<const mcaq_h4v*>(p));
+  }
+  static __device__ __forceinline__ mcaq_f4v widen(pk4 v) { return __builtin_convertvector(v, mcaq_f4v); }
   static __device__ __forceinline__ float ld(const _Float16* p) { return (float)*p; }
   template <bool NT> static __device__ __forceinline__ mcaq_f4v ld4(const _Float16* p) {
     return __builtin_convertvector(ld_v<NT>(reinterpret_cast<const mcaq_h4v*>(p)), mcaq_f4v);
   }
   static __device__ __forceinline__ float2 ld2(const _Float16* p) { return make_float2((float)p[0], (float)p[1]); }
+  static __device__ __forceinline__ void st(_Float16* p, float v) { *p = (_Float16)v; }
+  template <bool NT> static __device__ __forceinline__ void st4(_Float16* p, mcaq_f4v v) {
+    st_v<NT>(reinterpret_cast<mcaq_h4v*>(p), __builtin_convertvector(v, mcaq_h4v));
+  }
 };
 struct Bf16 { unsigned short u; };
 template <> struct ElemIO<Bf16> {
+  typedef mcaq_u4v pk4;
+  static __device__ __forceinline__ unsigned short ldp(const Bf16* p) { return p->u; }
+  template <bool NT> static __device__ __forceinline__ pk4 ldp4(const Bf16* p) {
+    return ld_v<NT>(reinterpret_cast<const mcaq_u4v*>(p));
+  }
+  static __device__ __forceinline__ mcaq_f4v widen(pk4 v) {
+    return mcaq_f4v{bf16_f(v.x), bf16_f(v.y), bf16_f(v.z), bf16_f(v.w)};
+  }
   static __device__ __forceinline__ float ld(const Bf16* p) { return bf16_f(p->u); }
   template <bool NT> static __device__ __forceinline__ mcaq_f4v ld4(const Bf16* p) {
     const mcaq_u4v u = ld_v<NT>(reinterpret_cast<const mcaq_u4v*>(p));
     return mcaq_f4v{bf16_f(u.x), bf16_f(u.y), bf16_f(u.z), bf16_f(u.w)};
   }
   static __device__ __forceinline__ float2 ld2(const Bf16* p) { return make_float2(bf16_f(p[0].u), bf16_f(p[1].u)); }
+  static __device__ __forceinline__ void st(Bf16* p, float v) { p->u = bf16_rne(v); }
+  template <bool NT> static __device__ __forceinline__ void st4(Bf16* p, mcaq_f4v v) {
+    st_v<NT>(reinterpret_cast<mcaq_u4v*>(p), mcaq_u4v{bf16_rne(v.x), bf16_rne(v.y), bf16_rne(v.z), bf16_rne(v.w)});
+  }
 };
 
 // Fold one 16-row block sum into cascade levels a1..a3 (Cascade::push at i % 16 == 0).

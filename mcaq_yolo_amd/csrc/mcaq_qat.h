@@ -16,6 +16,8 @@
 // The HBM traffic: forward reads x (+ m plane) and writes y; backward reads
 // g and x (+ m) and writes grad_x, plus per-slice channel partials of the two
 // sums ((C/32) x 2 planes of B*H*W floats) that a small per-image kernel folds.
+// x and grad_x may be fp16 / bf16 (mcaq_qat_scale.dtype, the maps of an
+// autocast step): 2 B instead of 4 for each of them, the arithmetic unchanged.
 #pragma once
 
 namespace mcaq {
@@ -182,8 +184,18 @@ __device__ __forceinline__ void qat_budget_block(const QatBudget& B, float* red)
 // kTile: every scale's map is a power-of-two multiple of its tile grid with
 // tiles >= 4 pixels wide (host-checked): a lane's 4 pixels share one tile, so
 // one bit-map load and one (lo, hi) table pair per channel serve all four
-template <bool kBwd, bool kVec, bool kTile = false>
-__global__ __launch_bounds__(256, MCAQ_QAT_MINW) void mcaq_qat_kernel(QatArgs a) {
+// T: the element type of x and grad_x (mcaq_qat_scale.dtype).  An fp16 / bf16
+// x widens exactly at the load (ElemIO<T>: one 8-byte load of a lane's four
+// pixels on the vector path) and everything after the load is the fp32
+// kernel's, so y and the two sums are those of the fp32 kernel on x.float();
+// grad_x is rounded once to T at the store (8 bytes a lane on the vector path).
+// The element-wise (!kVec) half kernels get one wave per SIMD less: under the
+// 128-register cap of MCAQ_QAT_MINW = 4 their backward spills (8-12 B a lane;
+// the fp32 one, left as it was, does too)
+template <bool kVec, typename T>
+constexpr int qat_minw() { return (kVec || sizeof(T) == 4 || MCAQ_QAT_MINW < 2) ? MCAQ_QAT_MINW : MCAQ_QAT_MINW - 1; }
+template <bool kBwd, bool kVec, bool kTile = false, typename T = float>
+__global__ __launch_bounds__(256, (qat_minw<kVec, T>())) void mcaq_qat_kernel(QatArgs a) {
   __shared__ float4 qt[32 * QAT_NB];   // scale, zp, 1/scale
   __shared__ float red[2][4][256];
   __shared__ int s_last;   // bands completed by this unit (bit per band)
@@ -209,22 +221,22 @@ __global__ __launch_bounds__(256, MCAQ_QAT_MINW) void mcaq_qat_kernel(QatArgs a)
   const int cw = wv * 8;
   const int ncw = imin_(8, nc - cw);
   const size_t rowbase = ((size_t)b * S.C + c0 + imax_(0, imin_(cw, nc - 1))) * HW;
-  const float* xb = S.x + rowbase;
+  const T* xb = reinterpret_cast<const T*>(S.x) + rowbase;
   const int qa = q0 < HW ? q0 : 0;
   // ---- the wave's 8 x rows first, unconditionally (clamped channel and
   // pixel indices): in flight through the table build and the per-pixel
   // prologue, as pass 2 issues them (the backward's g rows follow in the
   // channel loop: both sets at once spill 84 B a lane at 128 VGPRs)
-  float xv[8][4];
+  // (a half row stays packed, two registers a lane, until its channel's turn)
+  typename ElemIO<T>::pk4 xv[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const size_t ro = (size_t)imin_(c, imax_(ncw - 1, 0)) * HW;
     if (kVec) {
-      const float4 t = *reinterpret_cast<const float4*>(xb + ro + qa);
-      xv[c][0] = t.x; xv[c][1] = t.y; xv[c][2] = t.z; xv[c][3] = t.w;
+      xv[c] = ElemIO<T>::template ldp4<false>(xb + ro + qa);
     } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) xv[c][k] = xb[ro + imin_(q0 + k, HW - 1)];
+      for (int k = 0; k < 4; ++k) xv[c][k] = ElemIO<T>::ldp(xb + ro + imin_(q0 + k, HW - 1));
     }
   }
   for (int i = tid; i < nc * QAT_NB; i += 256) {
@@ -277,7 +289,7 @@ __global__ __launch_bounds__(256, MCAQ_QAT_MINW) void mcaq_qat_kernel(QatArgs a)
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     if (c >= ncw) break;
-    const float* v = xv[c];
+    const mcaq_f4v v = ElemIO<T>::widen(xv[c]);
     float gv[4];
     if (kBwd) {
       const size_t ro = (size_t)c * HW;
@@ -313,14 +325,24 @@ __global__ __launch_bounds__(256, MCAQ_QAT_MINW) void mcaq_qat_kernel(QatArgs a)
         sgf[k] += gm * qh - gm * ql;
       }
     }
-    float* orow = (kBwd ? S.gx : S.y) + rowbase + (size_t)c * HW;
-    if (kVec) {
-      typedef float f4v __attribute__((ext_vector_type(4)));
-      const f4v ov = {o[0], o[1], o[2], o[3]};
-      if (pv[0]) __builtin_nontemporal_store(ov, reinterpret_cast<f4v*>(orow + q0));   // written once, streamed
-    } else {
+    // y is fp32 on every map; grad_x has the map's type (written once, streamed)
+    const mcaq_f4v ov = {o[0], o[1], o[2], o[3]};
+    if constexpr (kBwd) {
+      T* orow = reinterpret_cast<T*>(S.gx) + rowbase + (size_t)c * HW;
+      if (kVec) {
+        if (pv[0]) ElemIO<T>::template st4<true>(orow + q0, ov);
+      } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) if (pv[k]) orow[q0 + k] = o[k];
+        for (int k = 0; k < 4; ++k) if (pv[k]) ElemIO<T>::st(orow + q0 + k, o[k]);
+      }
+    } else {
+      float* orow = S.y + rowbase + (size_t)c * HW;
+      if (kVec) {
+        if (pv[0]) ElemIO<float>::template st4<true>(orow + q0, ov);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (pv[k]) orow[q0 + k] = o[k];
+      }
     }
   }
   if (!kBwd) return;
@@ -443,7 +465,6 @@ __global__ __launch_bounds__(256) void mcaq_ema_multi_kernel(EmaMulti M) { ema_m
 }  // namespace mcaq
 
 namespace mcaq {
-// 16-byte vector rows need 16-byte aligned bases of every per-element array
 // the EMA segments of a launch; returns its workgroup count, or -1
 static inline int ema_multi_args(const mcaq_ema_seg* segs, int nseg, EmaMulti& M) {
   int wg = 0;
@@ -467,10 +488,34 @@ static inline bool qat_tile_ok(const mcaq_qat_scale* sc, int n) {
   }
   return true;
 }
-static inline bool qat_aligned16(const mcaq_qat_scale& s, bool bwd) {
-  uintptr_t u = (uintptr_t)s.x;
-  u |= bwd ? ((uintptr_t)s.g | (uintptr_t)s.gx) : (uintptr_t)s.y;
-  return (u & 15) == 0;
+// the vector path's rows: a lane's four elements are 16 bytes of the fp32
+// arrays (g, y, an fp32 x / grad_x) and 8 bytes of an fp16 / bf16 x / grad_x,
+// each base aligned to its own width
+static inline bool qat_vec_aligned(const mcaq_qat_scale& s, bool bwd) {
+  const uintptr_t xa = s.dtype == MCAQ_DTYPE_F32 ? 15 : 7;
+  if ((uintptr_t)s.x & xa) return false;
+  if (bwd) return ((uintptr_t)s.g & 15) == 0 && ((uintptr_t)s.gx & xa) == 0;
+  return ((uintptr_t)s.y & 15) == 0;
+}
+// one of the three kernels (tile + vector, vector, scalar) at the launch's
+// element type (qat_args: one per launch); no shape or alignment upcasts
+template <bool kBwd, typename T>
+static void qat_launch_t(int path, int grid, hipStream_t stream, const QatArgs& a) {
+  if (path == 2) launch_k((mcaq_qat_kernel<kBwd, true, true, T>), dim3(grid), dim3(256), 0, stream, a);
+  else if (path == 1) launch_k((mcaq_qat_kernel<kBwd, true, false, T>), dim3(grid), dim3(256), 0, stream, a);
+  else launch_k((mcaq_qat_kernel<kBwd, false, false, T>), dim3(grid), dim3(256), 0, stream, a);
+}
+template <bool kBwd>
+static void qat_launch(const mcaq_qat_scale* scales, int nscales, int grid, hipStream_t stream, const QatArgs& a) {
+  bool vec = true;
+  for (int i = 0; i < nscales; ++i)
+    vec = vec && ((scales[i].H * scales[i].W) & 3) == 0 && qat_vec_aligned(scales[i], kBwd);
+  const int path = !vec ? 0 : (qat_tile_ok(scales, nscales) ? 2 : 1);
+  switch (scales[0].dtype) {
+    case MCAQ_DTYPE_F16: qat_launch_t<kBwd, _Float16>(path, grid, stream, a); break;
+    case MCAQ_DTYPE_BF16: qat_launch_t<kBwd, Bf16>(path, grid, stream, a); break;
+    default: qat_launch_t<kBwd, float>(path, grid, stream, a); break;
+  }
 }
 }  // namespace mcaq
 
@@ -486,6 +531,8 @@ static int qat_args(const mcaq_qat_scale* scales, int nscales, bool bwd, mcaq::Q
   blocks = 0;
   for (int i = 0; i < nscales; ++i) {
     const mcaq_qat_scale& s = scales[i];
+    if (s.dtype != scales[0].dtype || s.dtype < MCAQ_DTYPE_F32 || s.dtype > MCAQ_DTYPE_BF16)
+      return (int)hipErrorInvalidValue;    // one element type of x / grad_x per launch
     if (s.B < 1 || s.C < 1 || s.H < 1 || s.W < 1 || s.ht < 1 || s.wt < 1 || s.ht > s.H || s.wt > s.W ||
         s.W > QAT_FOLD_LDS ||
         !s.x || !s.bits || !s.xmin || !s.xmax)
@@ -510,15 +557,7 @@ int mcaq_qat_forward(const mcaq_qat_scale* scales, int nscales, hipStream_t stre
   int blocks;
   const int e = qat_args(scales, nscales, false, a, blocks);
   if (e) return e;
-  bool vec = true;
-  for (int i = 0; i < nscales; ++i)
-    vec = vec && ((scales[i].H * scales[i].W) & 3) == 0 && mcaq::qat_aligned16(scales[i], false);
-  if (vec && mcaq::qat_tile_ok(scales, nscales))
-    launch_k((mcaq::mcaq_qat_kernel<false, true, true>), dim3(a.units_total), dim3(256), 0, stream, a);
-  else if (vec)
-    launch_k((mcaq::mcaq_qat_kernel<false, true>), dim3(a.units_total), dim3(256), 0, stream, a);
-  else
-    launch_k((mcaq::mcaq_qat_kernel<false, false>), dim3(a.units_total), dim3(256), 0, stream, a);
+  mcaq::qat_launch<false>(scales, nscales, a.units_total, stream, a);
   return (int)hipGetLastError();
 }
 
@@ -535,15 +574,7 @@ int mcaq_qat_forward_budget(const mcaq_qat_scale* scales, int nscales, const flo
     a.bb.n[k] = n[k];
   }
   a.bb.nseg = nseg; a.bb.target = target; a.bb.avg = avg; a.bb.loss = loss;
-  bool vec = true;
-  for (int i = 0; i < nscales; ++i)
-    vec = vec && ((scales[i].H * scales[i].W) & 3) == 0 && mcaq::qat_aligned16(scales[i], false);
-  if (vec && mcaq::qat_tile_ok(scales, nscales))
-    launch_k((mcaq::mcaq_qat_kernel<false, true, true>), dim3(a.units_total + 1), dim3(256), 0, stream, a);
-  else if (vec)
-    launch_k((mcaq::mcaq_qat_kernel<false, true>), dim3(a.units_total + 1), dim3(256), 0, stream, a);
-  else
-    launch_k((mcaq::mcaq_qat_kernel<false, false>), dim3(a.units_total + 1), dim3(256), 0, stream, a);
+  mcaq::qat_launch<false>(scales, nscales, a.units_total + 1, stream, a);
   return (int)hipGetLastError();
 }
 
@@ -552,15 +583,7 @@ int mcaq_qat_backward(const mcaq_qat_scale* scales, int nscales, hipStream_t str
   int blocks;
   const int e = qat_args(scales, nscales, true, a, blocks);
   if (e) return e;
-  bool vec = true;
-  for (int i = 0; i < nscales; ++i)
-    vec = vec && ((scales[i].H * scales[i].W) & 3) == 0 && mcaq::qat_aligned16(scales[i], true);
-  if (vec && mcaq::qat_tile_ok(scales, nscales))
-    launch_k((mcaq::mcaq_qat_kernel<true, true, true>), dim3(a.units_total), dim3(256), 0, stream, a);
-  else if (vec)
-    launch_k((mcaq::mcaq_qat_kernel<true, true>), dim3(a.units_total), dim3(256), 0, stream, a);
-  else
-    launch_k((mcaq::mcaq_qat_kernel<true, false>), dim3(a.units_total), dim3(256), 0, stream, a);
+  mcaq::qat_launch<true>(scales, nscales, a.units_total, stream, a);
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) return (int)le;
   // the separate fold only for scales without arrival counters

@@ -2064,7 +2064,7 @@ __global__ __launch_bounds__(256) void mcaq_pack_kernel(PackArgs a, float* __res
 
 // the train step's blob pack riding on its pass-1 launch as workgroups
 // units_total.. (pass 1 reads no blob; the morph launch that follows does)
-template <bool kVec>
+template <bool kVec, typename T = float>
 __global__ __launch_bounds__(256, MCAQ_STATS_MINW) void mcaq_stats_pack_kernel(StatsArgs a, PackArgs p,
                                                                              float* __restrict__ out) {
   __shared__ float lds[ST_LDS];
@@ -2072,7 +2072,7 @@ __global__ __launch_bounds__(256, MCAQ_STATS_MINW) void mcaq_stats_pack_kernel(S
     pack_elem(p, out, ((int)blockIdx.x - a.units_total) * 256 + (int)threadIdx.x);
     return;
   }
-  stats_dispatch<kVec>(a, lds, (int)blockIdx.x);
+  stats_dispatch<kVec, T>(a, lds, (int)blockIdx.x);
 }
 
 }  // namespace mcaq
@@ -3089,15 +3089,19 @@ int mcaq_stats_pack(const mcaq_stats_scale* scales, int nscales, const mcaq_pack
   bool vec;
   const int e = stats_args(scales, nscales, a, vec);
   if (e) return e;
-  if (scales[0].dtype != MCAQ_DTYPE_F32) return (int)hipErrorNotSupported;   // the train step's x is fp32
   PackArgs p{};
   const int pe = pack_args(segs, nseg, out, total, p);
   if (pe) return pe;
   const dim3 g(a.units_total + (total + 255) / 256);
-  if (vec)
-    launch_k(mcaq_stats_pack_kernel<true>, g, dim3(256), 0, stream, a, p, out);
-  else
-    launch_k(mcaq_stats_pack_kernel<false>, g, dim3(256), 0, stream, a, p, out);
+  // the element types of mcaq_stats (an autocast step's maps are fp16 / bf16)
+  switch (scales[0].dtype * 2 + (vec ? 1 : 0)) {
+    case 0: launch_k(mcaq_stats_pack_kernel<false>, g, dim3(256), 0, stream, a, p, out); break;
+    case 1: launch_k(mcaq_stats_pack_kernel<true>, g, dim3(256), 0, stream, a, p, out); break;
+    case 2: launch_k((mcaq_stats_pack_kernel<false, _Float16>), g, dim3(256), 0, stream, a, p, out); break;
+    case 3: launch_k((mcaq_stats_pack_kernel<true, _Float16>), g, dim3(256), 0, stream, a, p, out); break;
+    case 4: launch_k((mcaq_stats_pack_kernel<false, Bf16>), g, dim3(256), 0, stream, a, p, out); break;
+    default: launch_k((mcaq_stats_pack_kernel<true, Bf16>), g, dim3(256), 0, stream, a, p, out); break;
+  }
   return (int)hipGetLastError();
 }
 

@@ -246,6 +246,7 @@ def _run_analyzer_multi(an, xs):
         s = stats[i]
         s.x, s.gray, s.absmean, s.pmin, s.pmax = _p(x), _p(o["gray"]), _p(o["absmean"]), _p(o["pmin"]), _p(o["pmax"])
         s.B, s.C, s.H, s.W, s.Hc, s.Wc = B, C, H, W, ht * T, wt * T
+        s.dtype = core._ABI_DTYPES[x.dtype]      # fp16 / bf16 maps (HALF_NATIVE) widen exactly in pass 1
         ptrs = dict(gray=o["gray"], phi_out=o["phi"], tile_tmp=o["tile_tmp"], cmlp=blob, c_out=o["c"],
                     cmlp_out=o["craw"])
         scratch = L.mcaq_morph_scratch_bytes(B, ht * T, wt * T, ht, wt)
@@ -767,6 +768,22 @@ class _SoftMaskMulti(torch.autograd.Function):
 # _SoftMaskMulti / _QATMulti nodes and avg_bits as torch ops.
 FUSED_MASK_QAT = True
 
+# fp16 / bf16 feature maps (the maps of an autocast training step) are read by
+# pass 1 and by the QAT quantizer as they are, saved for the backward as they
+# are, and receive their gradient in their own dtype (mcaq_stats_scale.dtype,
+# mcaq_qat_scale.dtype; core.half_native is the condition).  The values are
+# those of the x.float() route bit for bit (the loads widen exactly, the
+# arithmetic is fp32, grad_x is rounded once as autograd's cast would).
+# False: every map is upcast first (two fp32 copies a map, one of them alive
+# until the backward, and a cast of grad_x).  Read at call time.
+HALF_NATIVE = True
+
+
+def _qat_maps(xs):
+    """The quantizer's maps of one step: themselves (core.half_native), else
+    their contiguous fp32 copies."""
+    return [x.detach() for x in xs] if core.half_native(*xs) else [_f32c(x) for x in xs]
+
 
 class _MaskQuantMulti(torch.autograd.Function):
     """LearnedSoftMask + fractional-bit STE quantizer of every scale, plus the
@@ -812,11 +829,11 @@ class _MaskQuantMulti(torch.autograd.Function):
                 abi.check(L.mcaq_morph_ema(morphs, n, segs_e, ne, None, None, None, 0, 0.0, st), "mcaq_morph_ema")
         else:
             abi.check(L.mcaq_morph(morphs, n, st), "mcaq_morph(soft mask)")
-        xs = [_f32c(x) for x in xs]
+        xs = _qat_maps(xs)
         arr = (abi.QatScale * n)()
         ys = []
         for i in range(n):
-            y = torch.empty_like(xs[i])
+            y = torch.empty(xs[i].shape, dtype=torch.float32, device=xs[i].device)
             ys.append(y)
             q = core._qat_struct(xs[i], bf[i], ms[i], mins[i], maxs[i])
             q.y = _p(y)
@@ -853,8 +870,8 @@ class _MaskQuantMulti(torch.autograd.Function):
         for i in range(n):
             x = xs[i]
             B, C, H, W = x.shape
-            g = _f32c(gys[i]) if gys[i] is not None else torch.zeros_like(x)
-            gx = torch.empty_like(x)
+            g = _f32c(gys[i]) if gys[i] is not None else torch.zeros(x.shape, device=x.device)
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)      # a half map's gradient in its dtype
             work = torch.empty(L.mcaq_qat_work_floats(B, C, H, W), device=x.device)
             keep += [g, work]
             q = core._qat_struct(x, bits[i], ms[i], mins[i], maxs[i])
@@ -915,13 +932,13 @@ class _QATMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, *args):
         xs, bits, ms, mins, maxs = (args[k * n:(k + 1) * n] for k in range(5))
-        xs = [_f32c(x) for x in xs]
+        xs = _qat_maps(xs)
         bits = [_f32c(b) for b in bits]
         ms = [None if m is None else _f32c(m) for m in ms]
         arr = (abi.QatScale * n)()
         ys = []
         for i in range(n):
-            y = torch.empty_like(xs[i])
+            y = torch.empty(xs[i].shape, dtype=torch.float32, device=xs[i].device)
             ys.append(y)
             q = core._qat_struct(xs[i], bits[i], ms[i], mins[i], maxs[i])
             q.y = _p(y)
@@ -947,8 +964,8 @@ class _QATMulti(torch.autograd.Function):
         for i in range(n):
             x = xs[i]
             B, C, H, W = x.shape
-            g = _f32c(gys[i]) if gys[i] is not None else torch.zeros_like(x)
-            gx = torch.empty_like(x)
+            g = _f32c(gys[i]) if gys[i] is not None else torch.zeros(x.shape, device=x.device)
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)      # a half map's gradient in its dtype
             gm = torch.empty(B, H, W, device=x.device) if (ms[i] is not None and ctx.needs_input_grad[1 + 2 * n + i]) \
                 else None
             gb = torch.empty(bits[i].shape, device=x.device) if ctx.needs_input_grad[1 + n + i] else None
@@ -1009,7 +1026,9 @@ def forward_features(hooks, feats, state):
     n = len(feats)
     an, mapper = hooks.complexity_analyzer, hooks.bit_mapper
     idxs = list(hooks.backbone_out_indices)[:n]
-    xs = [f.float().contiguous() for f in feats]
+    # half maps of an autocast step go to pass 1 and the quantizer as they are
+    # (HALF_NATIVE); otherwise every map as contiguous fp32
+    xs = [f.detach() for f in feats] if core.half_native(*feats) else [f.float().contiguous() for f in feats]
     box = []
     qs = [hooks.quantizers[str(i)] for i in idxs]
     smods = [q.soft_mask for q in qs]
