@@ -89,13 +89,6 @@ static inline int stats_ppl(int C, int HW) {
 // ATen's amin/amax propagate NaN): unlike fminf/fmaxf in IEEE mode they need
 // no v_max_f32 canonicalisation of loaded or DPP-moved operands, which was a
 // third of pass 1's min/max VALU work.  Exact in any order.
-#ifndef MCAQ_STATS_PERMLANE
-#define MCAQ_STATS_PERMLANE 0
-#endif
-#ifndef MCAQ_STATS_TAIL_PXMAJOR   // tail items pixel-major over the lanes (A/B)
-#define MCAQ_STATS_TAIL_PXMAJOR 0
-#endif
-
 __device__ __forceinline__ float vmin_(float a, float b) { return __builtin_elementwise_minimum(a, b); }
 __device__ __forceinline__ float vmax_(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 template <int CTRL>
@@ -119,26 +112,8 @@ __device__ __forceinline__ void wave_minmax16(float (&mn)[ST_CG], float (&mx)[ST
   rs_step<2, 0x4E>(mn, mx, (lane & 2) != 0);    // quad_perm 2301 (l ^ 2)
   rs_step<1, 0xB1>(mn, mx, (lane & 1) != 0);    // quad_perm 1032 (l ^ 1)
   float a = mn[0], b = mx[0];
-#if MCAQ_STATS_PERMLANE
-  // cross-row exchanges on the VALU (gfx950 v_permlane16_swap / 32_swap with
-  // the value as both operands: each lane sees its own value and lane l ^ 16
-  // (l ^ 32) among the two results) instead of two LDS bpermutes per step
-  {
-    const auto pa = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-    const auto pb = __builtin_amdgcn_permlane16_swap(__float_as_uint(b), __float_as_uint(b), false, false);
-    a = vmin_(vmin_(a, __uint_as_float(pa[0])), __uint_as_float(pa[1]));
-    b = vmax_(vmax_(b, __uint_as_float(pb[0])), __uint_as_float(pb[1]));
-  }
-  {
-    const auto pa = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-    const auto pb = __builtin_amdgcn_permlane32_swap(__float_as_uint(b), __float_as_uint(b), false, false);
-    a = vmin_(vmin_(a, __uint_as_float(pa[0])), __uint_as_float(pa[1]));
-    b = vmax_(vmax_(b, __uint_as_float(pb[0])), __uint_as_float(pb[1]));
-  }
-#else
   a = vmin_(a, __shfl_xor(a, 16, 64)); b = vmax_(b, __shfl_xor(b, 16, 64));
   a = vmin_(a, __shfl_xor(a, 32, 64)); b = vmax_(b, __shfl_xor(b, 32, 64));
-#endif
   omn = a; omx = b;
 }
 
@@ -307,7 +282,7 @@ __device__ __noinline__ float seq_sum(const T* xb, int HW, int p, int C) {
 // order instead: their 4 x ceil(C/64) independent 16-row block sums are spread
 // over the workgroup (one load round trip), then folded per pixel.
 template <int PPL, bool kVec, typename T>
-__device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, float* lds, const int only_round = -1) {
+__device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, float* lds) {
   float (*bsg)[256] = reinterpret_cast<float (*)[256]>(lds);
   float (*bsa)[256] = reinterpret_cast<float (*)[256]>(lds + ST_WAVES * 256);
   constexpr int UPIX = 64 * PPL;
@@ -318,11 +293,7 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
   const int C = S.C;
   const T* xb = reinterpret_cast<const T*>(S.x) + (size_t)b * C * HW;
   const bool cropped = (S.Hc != S.H) || (S.Wc != S.W);
-#ifdef MCAQ_PROBE_STATS_NO_MINMAX   // timing probe only (no min/max partials)
-  const bool want_g = S.gray != nullptr, want_a = S.absmean != nullptr, want_m = false;
-#else
   const bool want_g = S.gray != nullptr, want_a = S.absmean != nullptr, want_m = S.pmin != nullptr;
-#endif
   const int base = chunk * UPIX;
   const int q0 = base + lane * PPL;                    // first pixel of this lane
   bool pv[PPL];
@@ -337,34 +308,9 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
   const int ntail = tend - tstart;
   const int nilp = C >> 2;                        // rows per interleaved cascade
   const int nbt = (nilp + 15) >> 4;               // 16-row blocks per cascade
-#ifdef MCAQ_PROBE_STATS_NO_TAIL   // timing probe only (wrong tail sums): tools/probe/stats_probe.sh
-  const bool need_tail = false;
-#else
   const bool need_tail = ntail > 0 && (want_a || (want_g && !cropped));
-#endif
   const bool coop = nbt <= 16;                    // 31 px x 4 x 16 x 2 floats fit the LDS
   const int titems = need_tail && coop ? ntail * 4 * nbt : 0;
-#ifdef MCAQ_STATS_TAIL_EARLY
-  // the tail's strided loads are issued before the channel rounds, so their
-  // latency overlaps the rounds' instead of following them (C <= 512)
-  constexpr int TE = 1;
-  const bool early = PPL == 1 && titems > 0 && titems <= TE * 256;   // the many-channel scales
-  float tv[TE][16];
-  if (early) {
-#pragma unroll
-    for (int e2 = 0; e2 < TE; ++e2) {
-      const int it = imin_(tid + e2 * 256, titems - 1);
-      const int i = it / (4 * nbt), rem = it - i * (4 * nbt);
-      const int k = rem / nbt, j = rem - k * nbt;
-      const int p = tstart + i;
-      const int r0 = 16 * j, n = imin_(16, nilp - r0);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) tv[e2][e] = ElemIO<T>::ld(xb + (size_t)(4 * (r0 + (e < n ? e : 0)) + k) * HW + p);
-    }
-  }
-#else
-  constexpr bool early = false;
-#endif
 
   Fold fg, fa;   // pixel `tid` (tid < UPIX)
   fg.init(); fa.init();
@@ -372,54 +318,6 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
   // * PPL = 64 floats per lane), so a unit with several channel rounds still
   // pays about one memory latency per MR rounds
   constexpr int MR = MCAQ_STATS_LANE_FLOATS / (ST_CG * PPL) > 0 ? MCAQ_STATS_LANE_FLOATS / (ST_CG * PPL) : 1;
-#ifdef MCAQ_PROBE_STATS_SPLIT
-  // timing probe only (wrong outputs): this workgroup loads one channel round
-  // of the unit and stores its block sums, no fold, no tail
-  if (only_round >= 0) {
-    const int r = only_round;
-    const int blk = imin_(r * ST_WAVES + wv, nblk - 1);
-    const int c0 = blk * ST_CG, nc = imin_(ST_CG, C - c0);
-    const int qa = pv[0] ? q0 : 0;
-    float v[ST_CG][PPL];
-#pragma unroll
-    for (int i = 0; i < ST_CG; ++i) {
-      const T* row = xb + (size_t)(c0 + (i < nc ? i : 0)) * HW;
-      if (kVec && PPL == 4) {
-        const mcaq_f4v t = ElemIO<T>::template ld4<true>(row + qa);
-        v[i][0] = t.x; v[i][1 % PPL] = t.y; v[i][2 % PPL] = t.z; v[i][3 % PPL] = t.w;
-      } else {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) v[i][k] = ElemIO<T>::ld(row + imin_(q0 + k, HW - 1));
-      }
-    }
-    float gb[PPL], ab[PPL];
-#pragma unroll
-    for (int k = 0; k < PPL; ++k) { gb[k] = 0.0f; ab[k] = 0.0f; }
-#pragma unroll
-    for (int i = 0; i < ST_CG; ++i)
-      if (i < nc) {
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) { gb[k] = gb[k] + v[i][k]; ab[k] = ab[k] + fabsf(v[i][k]); }
-      }
-    if (want_m) {
-      float mn[ST_CG], mx[ST_CG];
-#pragma unroll
-      for (int i = 0; i < ST_CG; ++i) {
-        float lo = v[i][0], hi = v[i][0];
-#pragma unroll
-        for (int k = 1; k < PPL; ++k) { lo = vmin_(lo, v[i][k]); hi = vmax_(hi, v[i][k]); }
-        mn[i] = lo; mx[i] = hi;
-      }
-      float omn, omx;
-      wave_minmax16(mn, mx, lane, omn, omx);
-      if (lane < 16 && lane < nc) { S.pmin[(size_t)lu * C + c0 + lane] = omn; S.pmax[(size_t)lu * C + c0 + lane] = omx; }
-    }
-#pragma unroll
-    for (int k = 0; k < PPL; ++k)
-      if (pv[k] && want_g) S.gray[(size_t)b * HW + q0 + k] = gb[k] + ab[k];
-    return;
-  }
-#endif
   for (int r0 = 0; r0 < rounds; r0 += MR) {
     float v[MR][ST_CG][PPL];
     const int qa = pv[0] ? q0 : 0;
@@ -436,11 +334,7 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
           // streaming load: x is far larger than L2, and leaving L2 to the
           // morphology of the other in-flight batches gains ~3 % per step
           // (profiles/r01_stats_ntl_ab/)
-#if defined(MCAQ_STATS_PLAIN_LOADS)
-          const mcaq_f4v t = ElemIO<T>::template ld4<false>(row + qa);
-#else
           const mcaq_f4v t = ElemIO<T>::template ld4<true>(row + qa);
-#endif
           v[rr][i][0] = t.x; v[rr][i][1 % PPL] = t.y; v[rr][i][2 % PPL] = t.z; v[rr][i][3 % PPL] = t.w;
         } else if (kVec && PPL == 2) {
           const float2 t = ElemIO<T>::ld2(row + qa);
@@ -476,7 +370,7 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
           // in the image or the lane loaded pixels 0.. of the same channel row
           // (qa = 0 / clamped index) - genuine values, which cannot move a min
           // or max over the batch (r02 probe: the masks were ~1/3 of pass 1's
-          // min/max VALU work, tools/probe/stats_probe.sh)
+          // min/max VALU work)
           float mn[ST_CG], mx[ST_CG];
 #pragma unroll
           for (int i = 0; i < ST_CG; ++i) {
@@ -514,33 +408,11 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
     float* tsg = lds;                             // [px][k][j]
     float* tsa = lds + ST_LDS / 2;
     const int items = titems;
-#ifdef MCAQ_STATS_TAIL_EARLY
-    if (early) {
-#pragma unroll
-      for (int e2 = 0; e2 < TE; ++e2) {
-        const int it = tid + e2 * 256;
-        if (it < items) {
-          const int r0 = 16 * ((it % (4 * nbt)) % nbt), n = imin_(16, nilp - r0);
-          float sg = 0.0f, sa = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) if (e < n) { sg = sg + tv[e2][e]; sa = sa + fabsf(tv[e2][e]); }
-          tsg[it] = sg; tsa[it] = sa;
-        }
-      }
-    }
-#endif
-    for (int it = early ? items : tid; it < items; it += 256) {
-#if MCAQ_STATS_TAIL_PXMAJOR
-      // consecutive lanes on consecutive tail pixels of one (cascade, block):
-      // each load instruction touches a few rows, not one row per lane
-      const int i = it % ntail, rem = it / ntail;
-      const int k = rem / nbt, j = rem - k * nbt;
-      const int slot = (i * 4 + k) * nbt + j;
-#else
+    // (issuing these strided loads before the channel rounds, to overlap
+    // their latency, was measured and did not help)
+    for (int it = tid; it < items; it += 256) {
       const int i = it / (4 * nbt), rem = it - i * (4 * nbt);
       const int k = rem / nbt, j = rem - k * nbt;
-      const int slot = it;
-#endif
       const int p = tstart + i;
       const int r0 = 16 * j, n = imin_(16, nilp - r0);
       float v[16];
@@ -549,7 +421,7 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
       float sg = 0.0f, sa = 0.0f;
 #pragma unroll
       for (int e = 0; e < 16; ++e) if (e < n) { sg = sg + v[e]; sa = sa + fabsf(v[e]); }
-      tsg[slot] = sg; tsa[slot] = sa;
+      tsg[it] = sg; tsa[it] = sa;
     }
     __syncthreads();
     const int i = tid - (tstart - base);
@@ -606,18 +478,7 @@ __device__ __forceinline__ void stats_unit(const mcaq_stats_scale& S, int lu, fl
 // Permuted so that every unit of image b runs on XCD b % 8, the shared line
 // is fetched once and the neighbour reads it from that XCD's L2 (needs the
 // scale's block range to start at a multiple of 8 and B % 8 == 0; else the
-// plain order).  0: plain order (A/B).
-#ifndef MCAQ_STATS_XCD
-#define MCAQ_STATS_XCD 1
-#endif
-// > 0: pass 1 and pass 2 (tile kernel) launch at most MCAQ_STREAM_CAP
-// workgroups per CU (x 256 CUs, a multiple of 8: the XCD order holds) that
-// loop over their units, so the streaming passes never hold more than that
-// share of a CU and the latency-bound morphology of other batches in flight
-// finds room beside them.  0: one workgroup per unit (A/B).
-#ifndef MCAQ_STREAM_CAP
-#define MCAQ_STREAM_CAP 0
-#endif
+// plain order).
 
 template <bool kVec, typename T = float>   // kVec: 8/16-byte row accesses for ppl 2/4 (host checks alignment)
 __device__ __forceinline__ void stats_dispatch(const StatsArgs& a, float* lds, const int bid) {
@@ -628,7 +489,6 @@ __device__ __forceinline__ void stats_dispatch(const StatsArgs& a, float* lds, c
   int lu = unit - a.s[si].unit_begin;
   const mcaq_stats_scale S = a.s[si];   // wave-uniform index: scalar loads from the kernarg segment
   const int ppl = a.ppl[si];
-#if MCAQ_STATS_XCD && !defined(MCAQ_PROBE_STATS_SPLIT)
   {
     const int n = (si + 1 < a.nscales ? a.s[si + 1].unit_begin : a.units_total) - a.s[si].unit_begin;
     const int x0 = a.units_total - a.s[si].unit_begin - n;     // first blockIdx of this scale
@@ -638,36 +498,19 @@ __device__ __forceinline__ void stats_dispatch(const StatsArgs& a, float* lds, c
       lu = ((j & 7) + 8 * q) * upi + (slot - q * upi);
     }
   }
-#endif
-#ifdef MCAQ_PROBE_STATS_SPLIT
-  int rnd = -1;
-  {
-    const int nb = (S.C + ST_CG - 1) / ST_CG, R = (nb + ST_WAVES - 1) / ST_WAVES;
-    if (R >= 2) { rnd = lu % R; lu /= R; }
-  }
-#else
-  const int rnd = -1;
-#endif
   if constexpr (MCAQ_STATS_MAXPPL >= 4) {
-    if (ppl == 4) { stats_unit<4, kVec, T>(S, lu, lds, rnd); return; }
+    if (ppl == 4) { stats_unit<4, kVec, T>(S, lu, lds); return; }
   }
   if constexpr (MCAQ_STATS_MAXPPL >= 2) {
-    if (ppl == 2) { stats_unit<2, kVec, T>(S, lu, lds, rnd); return; }
+    if (ppl == 2) { stats_unit<2, kVec, T>(S, lu, lds); return; }
   }
-  stats_unit<1, kVec, T>(S, lu, lds, rnd);
+  stats_unit<1, kVec, T>(S, lu, lds);
 }
 
 template <bool kVec, typename T = float>
 __global__ __launch_bounds__(256, MCAQ_STATS_MINW) void mcaq_stats_kernel(StatsArgs a) {
   __shared__ float lds[ST_LDS];
-#if MCAQ_STREAM_CAP > 0
-  for (int u = (int)blockIdx.x; u < a.units_total; u += (int)gridDim.x) {
-    stats_dispatch<kVec, T>(a, lds, u);
-    __syncthreads();    // the LDS of this unit is free for the next
-  }
-#else
   stats_dispatch<kVec, T>(a, lds, (int)blockIdx.x);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -851,10 +694,6 @@ __global__ __launch_bounds__(256, MCAQ_BAND_MINW) void mcaq_band_kernel(MorphArg
   const int nb = band_count(S.Hc, S.tile);
   const int b = wg / nb;
   Ctx ctx{(int)threadIdx.x, 256};
-#ifdef MCAQ_TWICE   // diagnostic: a second, identical run finds the code in the instruction cache
-  band_pass(ctx, S, b, wg - b * nb, smem);
-  __syncthreads();
-#endif
   band_pass(ctx, S, b, wg - b * nb, smem);
 }
 
@@ -865,10 +704,6 @@ __global__ __launch_bounds__(256, MCAQ_EDGE_MINW) void mcaq_edge_kernel(MorphArg
   while (si + 1 < a.nscales && (int)blockIdx.x >= a.ewg_begin[si + 1]) ++si;
   const MorphScale& S = a.s[si];
   Ctx ctx{(int)threadIdx.x, 256};
-#ifdef MCAQ_TWICE
-  edge_image(ctx, S, (int)blockIdx.x - a.ewg_begin[si], smem);
-  __syncthreads();
-#endif
   edge_image(ctx, S, (int)blockIdx.x - a.ewg_begin[si], smem);
 }
 
@@ -1053,13 +888,10 @@ struct QuantArgs {
   float rnsl[MAXSEG], rupi[MAXSEG], rw[MAXSEG];
 };
 
-#ifndef MCAQ_QSLICE
-#define MCAQ_QSLICE 32
-#endif
-constexpr int QSLICE = MCAQ_QSLICE;   // channels per unit (8 per wave)
-// mcaq_quant_tile_kernel stores one [bits][channel] table entry per thread
-// (bit width tid / 32, channel tid % 32) for 8 widths x QSLICE channels
-static_assert(QSLICE == 32, "the tile-aligned pass 2 assumes 32-channel slices");
+// channels per unit (8 per wave).  Fixed: mcaq_quant_tile_kernel stores one
+// [bits][channel] table entry per thread (bit width tid / 32, channel tid % 32)
+// for 8 widths x QSLICE channels
+constexpr int QSLICE = 32;
 constexpr int QCW = QSLICE / 4;       // channels per wave
 constexpr int QMAXBITS = 15;   // max entries per channel in the LDS table
 constexpr int QMAXNT = 1024;   // max tiles per image whose m values are staged in LDS (more: read from L2)
@@ -1195,11 +1027,7 @@ __global__ MCAQ_QUANT_LB void mcaq_quant_kernel(QuantArgs a) {
     qhi[k] = (float)((1 << (bb - 1)) - 1);
   }
   __syncthreads();   // qt, mts ready
-#ifndef MCAQ_PROBE_Q_NOM
   if (kM == QM_MT_LDS || kM == QM_MT_L2) {
-#else
-  if (false) {
-#endif
     // m(p) = 5x5 Gaussian (replicate pad) of the nearest-upsampled tile values,
     // taps row-major from 0 - the m plane LearnedSoftMask produces
     // (quantization.py:235-238), generated here instead of read from HBM.
@@ -1240,11 +1068,7 @@ __global__ MCAQ_QUANT_LB void mcaq_quant_kernel(QuantArgs a) {
       const float4 sz = qt[(cw + c) * NB + kb[k]];
       QParam q;
       q.scale = sz.x; q.zp = sz.y; q.rs = sz.z; q.qmin = qlo[k]; q.qmax = qhi[k];
-#ifdef MCAQ_PROBE_Q_NOQ
-      float d = v[c][k] * q.scale;
-#else
       float d = any_x ? quant_dequant_any(v[c][k], q) : quant_dequant(v[c][k], q);
-#endif
       if (kM != QM_NONE) d = d * mv[k];
       o[k] = d;
     }
@@ -1276,38 +1100,9 @@ __global__ MCAQ_QUANT_LB void mcaq_quant_kernel(QuantArgs a) {
 // VALU instructions per wave on index arithmetic and its integer divisions:
 // rocprofv3 SQ_INSTS_VALU, profiles/r04_sq/).  Soft mask: none or m(tile)
 // values (QM_NONE / QM_MT_LDS); at most 8 bit widths.
-typedef float qt_f4v __attribute__((ext_vector_type(4)));
-
-// the x rows of one unit (8 x 16 B per lane) into v: step 2 of quant_tile_unit,
-// issued ahead of time by the pipelined kernel
-template <bool kNTL, typename T>
-__device__ __forceinline__ void quant_tile_load(const QuantArgs& a, const int unit, qt_f4v (&v)[QCW]) {
-  int si = 0;
-  while (si + 1 < a.nscales && unit >= a.s[si + 1].unit_begin) ++si;
-  const mcaq_quant_scale& S = a.s[si];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int HW = S.H * S.W;
-  const int nsl = (S.C + QSLICE - 1) / QSLICE, upi = (HW + 255) >> 8;
-  const int lu = unit - S.unit_begin;
-  const int q1 = div_small(lu, nsl, a.rnsl[si]);
-  const int slice = lu - q1 * nsl;
-  const int b = div_small(q1, upi, a.rupi[si]);
-  const int chunk = q1 - b * upi;
-  const int c0 = slice * QSLICE;
-  const int nc = imin_(QSLICE, S.C - c0);
-  const int q0 = chunk * 256 + lane * 4;
-  const int qa = q0 < HW ? q0 : 0;
-  const int cw = wv * QCW;
-  const int ncw = imin_(QCW, nc - cw);
-  const size_t rowbase = ((size_t)b * S.C + c0 + imax_(imin_(cw, nc - 1), 0)) * HW;
-  const T* xb = reinterpret_cast<const T*>(S.x) + rowbase;
-#pragma unroll
-  for (int c = 0; c < QCW; ++c) v[c] = ElemIO<T>::template ld4<kNTL>(xb + (size_t)imin_(c, imax_(ncw - 1, 0)) * HW + qa);
-}
-
-template <bool kNTL, bool kNTS, int kM, typename T, typename TO, bool kPre = false>
+template <bool kNTL, bool kNTS, int kM, typename T, typename TO>
 __device__ __forceinline__ void quant_tile_unit(const QuantArgs& a, const int unit, float4* qt, float* mts, float4* mq4,
-                                                int* qany, qt_f4v (*pre)[QCW] = nullptr) {
+                                                int* qany) {
   typedef float f2 __attribute__((ext_vector_type(2)));
   int si = 0;
   while (si + 1 < a.nscales && unit >= a.s[si + 1].unit_begin) ++si;
@@ -1347,13 +1142,8 @@ __device__ __forceinline__ void quant_tile_unit(const QuantArgs& a, const int un
   TO* yb = reinterpret_cast<TO*>(S.y) + rowbase;
   typedef float f4v __attribute__((ext_vector_type(4)));
   f4v v[QCW];
-  if constexpr (kPre) {
 #pragma unroll
-    for (int c = 0; c < QCW; ++c) v[c] = (*pre)[c];
-  } else {
-#pragma unroll
-    for (int c = 0; c < QCW; ++c) v[c] = ElemIO<T>::template ld4<kNTL>(xb + (size_t)imin_(c, imax_(ncw - 1, 0)) * HW + qa);
-  }
+  for (int c = 0; c < QCW; ++c) v[c] = ElemIO<T>::template ld4<kNTL>(xb + (size_t)imin_(c, imax_(ncw - 1, 0)) * HW + qa);
   // ---- 3. the table (IEEE divisions of QuantizationParameters), staged m(tile)
   {
     const int kq = imin_(tid >> 5, NB - 1);     // every thread stores an entry (unused rows harmless)
@@ -1435,45 +1225,7 @@ __global__ MCAQ_QUANT_LB void mcaq_quant_tile_kernel(QuantArgs a) {
   __shared__ float mts[kM == QM_MT_LDS ? QMAXNT : 1];
   __shared__ float4 mq4[64];                  // m(p) of each lane's 4 pixels
   __shared__ int qany[QSLICE];
-#if MCAQ_STREAM_CAP > 0
-  for (int u = (int)blockIdx.x; u < a.units_total; u += (int)gridDim.x) {
-    quant_tile_unit<kNTL, kNTS, kM, T, TO>(a, u, qt, mts, mq4, qany);
-    __syncthreads();    // LDS of this unit free for the next
-  }
-#else
   quant_tile_unit<kNTL, kNTS, kM, T, TO>(a, (int)blockIdx.x, qt, mts, mq4, qany);
-#endif
-}
-
-// Pipelined persistent form (MCAQ_QUANT_PIPE workgroups per CU, A/B): each
-// workgroup walks units u, u + grid, ...; the x rows of its NEXT unit are in
-// flight while the current one runs its prologue and stores (a 2-deep
-// register pipeline, as tools/probe/narrow_probe.hip's D2 copy).  Same
-// per-element arithmetic as mcaq_quant_tile_kernel.
-#ifndef MCAQ_QUANT_PIPE
-#define MCAQ_QUANT_PIPE 0
-#endif
-template <bool kNTL, bool kNTS, int kM, typename T = float, typename TO = T>
-__global__ __launch_bounds__(256, 2) void mcaq_quant_tile_pipe_kernel(QuantArgs a) {
-  __shared__ float4 qt[8 * QSLICE];
-  __shared__ float mts[kM == QM_MT_LDS ? QMAXNT : 1];
-  __shared__ float4 mq4[64];
-  __shared__ int qany[QSLICE];
-  qt_f4v va[QCW], vb[QCW];
-  const int grid = (int)gridDim.x, total = a.units_total;
-  int u = (int)blockIdx.x;
-  if (u < total) quant_tile_load<kNTL, T>(a, u, va);
-  for (; u < total; u += 2 * grid) {
-    const int un = u + grid;
-    if (un < total) quant_tile_load<kNTL, T>(a, un, vb);
-    quant_tile_unit<kNTL, kNTS, kM, T, TO, true>(a, u, qt, mts, mq4, qany, &va);
-    __syncthreads();
-    if (un >= total) break;
-    const int unn = un + grid;
-    if (unn < total) quant_tile_load<kNTL, T>(a, unn, va);
-    quant_tile_unit<kNTL, kNTS, kM, T, TO, true>(a, un, qt, mts, mq4, qany, &vb);
-    __syncthreads();
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1698,14 +1450,7 @@ __global__ MCAQ_QUANT_LB void mcaq_quant_tile_ref_kernel(QuantArgs a) {
   __shared__ float mts[kM == QM_MT_LDS ? QMAXNT : 1];
   __shared__ float4 mq4[64];
   __shared__ int qanyw[4 * QSLICE];           // [wave][c]: a flagged entry in the wave's width rows
-#if MCAQ_STREAM_CAP > 0
-  for (int u = (int)blockIdx.x; u < a.units_total; u += (int)gridDim.x) {
-    quant_tile_unit_ref<kM, T>(a, u, qt, mts, mq4, qanyw);
-    __syncthreads();
-  }
-#else
   quant_tile_unit_ref<kM, T>(a, (int)blockIdx.x, qt, mts, mq4, qanyw);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1771,12 +1516,6 @@ static int stats_args(const mcaq_stats_scale* scales, int nscales, StatsArgs& a,
       return (int)hipErrorInvalidValue;    // one element type per launch
     a.ppl[i] = stats_ppl(scales[i].C, HW);
     units += mcaq_stats_units(scales[i].B, scales[i].C, scales[i].H, scales[i].W);
-#ifdef MCAQ_PROBE_STATS_SPLIT
-    {
-      const int nb = (scales[i].C + ST_CG - 1) / ST_CG, R = (nb + ST_WAVES - 1) / ST_WAVES;
-      if (R >= 2) units += (R - 1) * mcaq_stats_units(scales[i].B, scales[i].C, scales[i].H, scales[i].W);
-    }
-#endif
   }
   a.nscales = nscales;
   a.units_total = units;
@@ -1791,7 +1530,7 @@ int mcaq_stats(const mcaq_stats_scale* scales, int nscales, hipStream_t stream) 
   bool vec;
   const int e = stats_args(scales, nscales, a, vec);
   if (e) return e;
-  const dim3 g(MCAQ_STREAM_CAP > 0 ? imin_(a.units_total, MCAQ_STREAM_CAP * 256) : a.units_total);
+  const dim3 g(a.units_total);
   switch (scales[0].dtype * 2 + (vec ? 1 : 0)) {
     case 0: launch_k(mcaq_stats_kernel<false>, g, dim3(256), 0, stream, a); break;
     case 1: launch_k(mcaq_stats_kernel<true>, g, dim3(256), 0, stream, a); break;
@@ -1853,12 +1592,7 @@ static int morph_plan(const MorphScale* s, int n, int* lds_mode, int* plane_stri
   for (int i = 0; i < n; ++i) pb = imax_(pb, (plane_bytes(s[i].Hc, s[i].Wc) + 15) & ~15);
   const int rest = fixed_bytes();   // pass A keeps no tile array in LDS
   const int limit = morph_lds_budget();
-#ifdef MCAQ_MORPH_GLOBAL_PLANES
-  const bool lds_fit = false;   // A/B: planes in global scratch (small LDS footprint beside streaming waves)
-#else
-  const bool lds_fit = pb + rest <= limit;
-#endif
-  if (lds_fit) {
+  if (pb + rest <= limit) {
     *lds_mode = 1; *plane_stride = pb; *dyn = (size_t)(pb + rest);
   } else if (rest <= limit) {
     *lds_mode = 0; *plane_stride = pb; *dyn = (size_t)rest;
@@ -1962,9 +1696,6 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
   bool band = any_phi != 0;
   for (int i = 0; i < nscales; ++i)
     if ((a.s[i].flags & F_PHI) && !band_eligible(a.s[i])) band = false;
-#ifdef MCAQ_NO_BAND
-  band = false;   // A/B: the per-image pass A
-#endif
   if (band) {
     int wg = 0, ewg = 0, dynb = 0, dyne = 0;
     for (int i = 0; i < nscales; ++i) {
@@ -2007,9 +1738,6 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
     }
     a.wg_begin[nscales] = wg;
     if (fa.nblocks > 0 && dyn < (size_t)(8 * MORPH_THREADS)) dyn = 8 * MORPH_THREADS;  // finalize_body's LDS
-#ifdef MCAQ_MORPH_EXCL
-    dyn = (size_t)limit;   // A/B: one pass-A workgroup per CU (no streaming waves beside it)
-#endif
     // canny_impl='legacy' is an analyzer option: one value for every scale of a launch
     const int leg = (a.s[0].flags & F_CANNY_LEGACY) ? 1 : 0;
     for (int i = 1; i < nscales; ++i)
@@ -2025,9 +1753,6 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
     // the soft mask's reference half arithmetic lives in the per-image pass B
     if (tf && (!tiles_batch_eligible(a.s[i]) || a.s[i].smask_arith != 0)) tb = false;
   }
-#ifdef MCAQ_NO_TILES_BATCH
-  tb = false;   // A/B: the per-image pass B
-#endif
   if (tb) {
     int blk = 0;
     for (int i = 0; i < nscales; ++i) {
@@ -2066,14 +1791,7 @@ static int morph_launch_config(const mcaq_morph_scale* scales, int nscales, cons
     if (per + TILES_SCRATCH_BYTES > lim) return (int)hipErrorInvalidValue;
     // stage the weight blobs in LDS when they fit beside the tile arrays and the MLP scratch
     L.wlds = per + TILES_SCRATCH_BYTES + weights_lds_bytes() <= lim;
-#ifdef MCAQ_TILES_NO_WLDS
-    L.wlds = 0;   // A/B: weights read through the caches (smaller LDS footprint per workgroup)
-#endif
-#ifdef MCAQ_TILES_EXCL
-    L.dyn_b = (size_t)lim;   // A/B: one pass-B workgroup per CU (no streaming waves beside it)
-#else
     L.dyn_b = (size_t)per + TILES_SCRATCH_BYTES + (L.wlds ? weights_lds_bytes() : 0);
-#endif
     L.grid_b = twg;
   }
   return 0;
@@ -2207,15 +1925,11 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
   // nontemporal policy (measured): bit 0 = streaming stores of
   // y, bit 1 = nontemporal loads of x.  NT stores always; NT loads only when
   // the launch reads > 256 MB of x (config 3), where nothing of x survives in
-  // L2/MALL anyway.  MCAQ_QUANT_NT (build-time define) pins it for A/B builds.
-#ifdef MCAQ_QUANT_NT
-  const int nt = MCAQ_QUANT_NT;
-#else
+  // L2/MALL anyway.
   size_t xbytes = 0;
   for (int i = 0; i < nscales; ++i)
     xbytes += (size_t)scales[i].B * scales[i].C * scales[i].H * scales[i].W * (scales[0].dtype ? 2 : sizeof(float));
   const int nt = xbytes > ((size_t)256 << 20) ? 3 : 1;
-#endif
   // m(p) source: one kind for every scale of the launch (the hook always
   // passes m(tile) values or nothing; the reference op a plane or nothing)
   int kind = -1;
@@ -2236,7 +1950,6 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     big = big || imin_(QSLICE, q.C) * q.nbits > 256 || (k == QM_MT_LDS && NT > 256);
   }
   const dim3 g(units), t(256);
-#ifndef MCAQ_TRUE_DIV
   // tile-aligned path: every scale's map a power-of-two multiple of its tile
   // grid (tiles >= 4 pixels wide), <= 8 bit widths, no plane / compat indexing
   bool tile_ok = vec && (kind == QM_NONE || kind == QM_MT_LDS);
@@ -2252,15 +1965,11 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     a.rupi[i] = 1.0f / (float)((q.H * q.W + 255) / 256);
     a.rw[i] = 1.0f / (float)q.W;
   }
-#ifdef MCAQ_NO_QUANT_TILE
-  tile_ok = false;   // A/B: the general kernel
-#endif
   const int dt = scales[0].dtype;
   if (dt != MCAQ_DTYPE_F32) {
     // fp16 / bf16 maps: the tile-aligned kernel only (any nontemporal policy:
     // NT loads and stores)
     if (!tile_ok) return (int)hipErrorNotSupported;
-    const dim3 g(MCAQ_STREAM_CAP > 0 ? imin_(units, MCAQ_STREAM_CAP * 256) : units);
     if (scales[0].arith == MCAQ_ARITH_REFERENCE) {
       switch ((kind == QM_NONE ? 0 : 1) + (dt == MCAQ_DTYPE_BF16 ? 2 : 0)) {
         case 0: launch_k(mcaq_quant_tile_ref_kernel<QM_NONE, _Float16>, g, t, 0, stream, a); break;
@@ -2278,24 +1987,7 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     }
     return (int)hipGetLastError();
   }
-#if MCAQ_QUANT_PIPE > 0
   if (tile_ok) {
-    const dim3 gp(imin_(units, MCAQ_QUANT_PIPE * 256));
-    switch ((kind == QM_NONE ? 0 : 4) + (nt & 3)) {
-      case 0: launch_k(mcaq_quant_tile_pipe_kernel<false, false, QM_NONE>, gp, t, 0, stream, a); break;
-      case 1: launch_k(mcaq_quant_tile_pipe_kernel<false, true, QM_NONE>, gp, t, 0, stream, a); break;
-      case 2: launch_k(mcaq_quant_tile_pipe_kernel<true, false, QM_NONE>, gp, t, 0, stream, a); break;
-      case 3: launch_k(mcaq_quant_tile_pipe_kernel<true, true, QM_NONE>, gp, t, 0, stream, a); break;
-      case 4: launch_k(mcaq_quant_tile_pipe_kernel<false, false, QM_MT_LDS>, gp, t, 0, stream, a); break;
-      case 5: launch_k(mcaq_quant_tile_pipe_kernel<false, true, QM_MT_LDS>, gp, t, 0, stream, a); break;
-      case 6: launch_k(mcaq_quant_tile_pipe_kernel<true, false, QM_MT_LDS>, gp, t, 0, stream, a); break;
-      default: launch_k(mcaq_quant_tile_pipe_kernel<true, true, QM_MT_LDS>, gp, t, 0, stream, a); break;
-    }
-    return (int)hipGetLastError();
-  }
-#endif
-  if (tile_ok) {
-    const dim3 g(MCAQ_STREAM_CAP > 0 ? imin_(units, MCAQ_STREAM_CAP * 256) : units);
     switch ((kind == QM_NONE ? 0 : 4) + (nt & 3)) {
       case 0: launch_k(mcaq_quant_tile_kernel<false, false, QM_NONE>, g, t, 0, stream, a); break;
       case 1: launch_k(mcaq_quant_tile_kernel<false, true, QM_NONE>, g, t, 0, stream, a); break;
@@ -2308,8 +2000,6 @@ int mcaq_quant(const mcaq_quant_scale* scales, int nscales, hipStream_t stream) 
     }
     return (int)hipGetLastError();
   }
-#endif
-  if (scales[0].dtype != MCAQ_DTYPE_F32) return (int)hipErrorNotSupported;   // fp16 / bf16: tile kernel only
 #define MCAQ_Q_LAUNCH(V, L, S_)                                                                              \
   do {                                                                                                       \
     switch (kind * 2 + (big ? 1 : 0)) {                                                                      \

@@ -235,18 +235,13 @@ MCAQ_HD QParam qparam(float xmin, float xmax, int b) {
 // 3 VALU ops instead of the ~10 of the v_div_scale/fmas/fixup sequence.  Where
 // it can differ - subnormal x, the sign of a zero quotient - the quotient
 // is < 1e-20 and the + zp that follows (0 or |zp| >= 6e-8) absorbs it, so
-// quant_dequant is unchanged.  MCAQ_TRUE_DIV builds keep the IEEE division.
+// quant_dequant is unchanged.
 // x / s, correctly rounded, for |x rs| < FLT_MAX (finite statistics cover x:
 // the fast path of pass 2)
 MCAQ_HD float div_by(float x, float s, float rs) {
-#ifdef MCAQ_TRUE_DIV
-  (void)rs;
-  return x / s;
-#else
   const float q0 = x * rs;
   const float r = fmaf(-q0, s, x);
   return fmaf(r, rs, q0);
-#endif
 }
 
 // The same for any x: when q0 = x rs is +-inf (x = +-inf, or an overflowing
@@ -262,14 +257,9 @@ MCAQ_HD float rem_finite(float r) {
 #endif
 }
 MCAQ_HD float div_by_any(float x, float s, float rs) {
-#ifdef MCAQ_TRUE_DIV
-  (void)rs;
-  return x / s;
-#else
   const float q0 = x * rs;
   const float r = rem_finite(fmaf(-q0, s, x));
   return fmaf(r, rs, q0);
-#endif
 }
 
 // clamp of a finite value into [lo, hi] (lo <= hi): one v_med3_f32 on the

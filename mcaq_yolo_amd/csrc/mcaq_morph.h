@@ -970,9 +970,7 @@ MCAQ_HD void morph_edges(const Ctx& ctx, const MorphScale& S, int b, int role, P
             for (int j = 0; j < 5; ++j) acc = fmaf(bits_as_float(k_gauss5_bits[i * 5 + j]), v[r + i][j], acc);
           if (r0 + r < Hc) {
             pl.A[(r0 + r) * Wc + w] = acc;
-#ifndef MCAQ_PROBE_NO_HIST   // timing probe only (wrong Otsu threshold)
             if (!legacy) otsu_hist_add(sh, acc);
-#endif
           }
         }
       }
@@ -1131,11 +1129,7 @@ MCAQ_HD void morph_edges(const Ctx& ctx, const MorphScale& S, int b, int role, P
             for (int i = 0; i < 11; ++i) m = fmaf(bits_as_float(k_g11_sep_bits[i]), v[r + i], m);
             const float g = pl.G[h * Wc + w] * 255.0f;
             const float t = m - 2.0f;
-#ifdef MCAQ_PROBE_NO_EXACT_G11   // timing probe only (separable estimate everywhere)
-            if (true) {
-#else
             if (fabsf(g - t) > marg) {
-#endif
               on[r] = g > t;
             } else {
               xlist[MATOMIC_FETCH_ADD(nx, 1)] = h * Wc + w;   // decided below
@@ -1213,10 +1207,8 @@ MCAQ_HD void morph_edges(const Ctx& ctx, const MorphScale& S, int b, int role, P
             gx = fmaf(-1.0f, z20, gx); gx = fmaf(1.0f, z22, gx);
             gy = fmaf(-1.0f, z00, gy); gy = fmaf(-2.0f, z01, gy); gy = fmaf(-1.0f, z02, gy);
             gy = fmaf(1.0f, z20, gy); gy = fmaf(2.0f, z21, gy); gy = fmaf(1.0f, z22, gy);
-#ifndef MCAQ_PROBE_NO_GRAD_PLANES   // timing probe only
             pl.A[h * Wc + w] = gx;
             pl.Bf[h * Wc + w] = gy;
-#endif
             // LBP (morphology.py:630-646): replicate pad, nb >= center, circular order
             int bt[8];
             bt[0] = c[r][0] >= ctr; bt[1] = c[r][1] >= ctr; bt[2] = c[r][2] >= ctr; bt[3] = c[r + 1][2] >= ctr;

@@ -5,6 +5,7 @@
 One hipcc invocation; the library links libamdhip64 by SONAME, so inside a
 Python process that imported torch first it binds to torch's HIP runtime (one
 runtime per process; checked by tests/test_lib_cpu.py on the GPU box)."""
+import glob
 import os
 import subprocess
 import sys
@@ -13,8 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcaq_yolo_amd", "csrc")
 OUT = os.path.join(ROOT, "mcaq_yolo_amd", "lib", "libmcaq_hip.so")
 SRCS = [os.path.join(CSRC, "mcaq_kernels.hip")]
-DEPS = SRCS + [os.path.join(CSRC, f) for f in ("mcaq_math.h", "mcaq_morph.h", "mcaq_band.h", "mcaq_tiles_batch.h", "mcaq_tables.h", "mcaq_mlp_mfma.h", "mcaq_qat.h", "mcaq_nms.h", "mcaq_train.h", "mcaq_optim.h", "mcaq_dp.h")] + \
-    [os.path.join(ROOT, "include", "mcaq_hip.h")]
+DEPS = SRCS + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "mcaq_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
          "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-result"]
@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 def build(force=False, verbose=True, stamps=False, defines=(), out=None):
     """defines / out: A/B variant builds (tools/gpu_ab.sh), e.g.
-    python tools/build.py --variant tools/probe/ab/x.so -DMCAQ_TILES_EXCL"""
+    python tools/build.py --variant tools/probe/ab/x.so -DMCAQ_TILES_MINW=2"""
     out = out or (OUT.replace(".so", "_stamps.so") if stamps else OUT)
     if not force and not defines and os.path.exists(out) and \
             all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS):
