@@ -521,6 +521,44 @@ typedef struct {
 } mcaq_qat_smask_seg;
 int mcaq_qat_smask_backward_multi(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_bit_budget* bb,
                                   hipStream_t stream);
+/* The tile-domain loss terms of a QAT step: the bit budget (the fields of
+ * mcaq_bit_budget, same meaning) and the smoothness term of the same bit maps,
+ * MCAQYOLOLoss.compute_smoothness_loss (models/mcaq_yolo.py:86-107):
+ *   S_k = (sum |b[:,1:,:] - b[:,:-1,:]| + sum |b[:,:,1:] - b[:,:,:-1]|) / max(1, n_edges_k),
+ *   n_edges_k = B ((ht - 1) wt + ht (wt - 1)),   L_smooth = (sum_k S_k) / nseg.
+ * The entries below are the siblings of mcaq_qat_forward_budget,
+ * mcaq_bit_budget_forward and mcaq_qat_smask_backward_multi, which remain and
+ * equal them with smooth = g_smooth = NULL.  Forward entries read target and
+ * smooth; the backward entry reads everything but smooth. */
+typedef struct {
+  const float* avg;      /* the forward's avg_bits (device scalar) */
+  const float* g_avg;    /* dL / d avg_bits, or NULL */
+  const float* g_loss;   /* dL / d loss, or NULL */
+  float target;
+  int nscales;           /* scales averaged by avg_bits and by L_smooth */
+  float* smooth;         /* forward: L_smooth (device scalar), or NULL: not computed */
+  const float* g_smooth; /* backward: dL / d L_smooth, or NULL: no smoothness gradient */
+} mcaq_tile_losses;
+/* mcaq_qat_forward_budget plus L_smooth (models/mcaq_yolo.py:86-107) from the
+ * same extra workgroup: per segment a strided sum per thread, then the means'
+ * fixed tree - deterministic, no further launch.  dims: nseg x (B, ht, wt) of
+ * the bit maps (every dimension >= 1), avg / loss as mcaq_qat_forward_budget. */
+int mcaq_qat_forward_tile_losses(const mcaq_qat_scale* scales, int nscales, const float* const* bits, const int* dims,
+                                 int nseg, float* avg, float* loss, const mcaq_tile_losses* tl, hipStream_t stream);
+/* mcaq_bit_budget_forward plus L_smooth (models/mcaq_yolo.py:86-107), one
+ * workgroup of its own: 1024 threads, a strided sum per thread, then the
+ * halving tree. */
+int mcaq_tile_losses_forward(const float* const* bits, const int* dims, int nseg, float* avg, float* loss,
+                             const mcaq_tile_losses* tl, hipStream_t stream);
+/* mcaq_qat_smask_backward_multi plus the gradient of L_smooth (models/
+ * mcaq_yolo.py:86-107) when g_smooth is set: per tile gbits = ((c + s kappa)
+ * + grad_bits(quantizer)) + grad_bits(soft mask), s = (g_smooth / nscales) /
+ * max(1, n_edges) of the tile's scale, kappa the integer sum of
+ * sign(b - b(neighbour)) over the tile's up to four neighbours inside its
+ * image (sign(0) = 0).  g_smooth NULL: bit for bit the values of
+ * mcaq_qat_smask_backward_multi. */
+int mcaq_qat_smask_backward_tile_losses(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_tile_losses* tl,
+                                        hipStream_t stream);
 typedef struct {
   const float* part;     /* [nparts][stride] partial sums */
   float* out;            /* count floats (chain: segment 0's only) */

@@ -102,6 +102,12 @@ class BitBudget(ctypes.Structure):
     _fields_ = [("avg", P), ("g_avg", P), ("g_loss", P), ("target", Fl), ("nscales", I)]
 
 
+class TileLosses(ctypes.Structure):
+    """mcaq_tile_losses: mcaq_bit_budget's fields, then the smoothness term's
+    forward output and upstream gradient."""
+    _fields_ = BitBudget._fields_ + [("smooth", P), ("g_smooth", P)]
+
+
 class QatSmaskSeg(ctypes.Structure):
     """mcaq_qat_smask_seg."""
     _fields_ = [("P", SmaskParams), ("bits", P), ("absmean", P), ("qat_work", P), ("gbits", P), ("gpart", P),
@@ -169,7 +175,8 @@ EXPORTS = ("mcaq_abi_version", "mcaq_launch_spatial_quantization", "mcaq_stats",
            "mcaq_ema_stats_multi_running", "mcaq_head_train_backward_multi_ride",
            "mcaq_stats_pack", "mcaq_morph_ema", "mcaq_mapper_train_backward_multi_ride", "mcaq_dp_unpack",
            "mcaq_mapper_sync_bytes", "mcaq_mapper_fused_max_wg", "mcaq_mapper_train_forward_fused",
-           "mcaq_mapper_train_backward_fused")
+           "mcaq_mapper_train_backward_fused",
+           "mcaq_qat_forward_tile_losses", "mcaq_tile_losses_forward", "mcaq_qat_smask_backward_tile_losses")
 
 _LIB = None
 
@@ -299,6 +306,14 @@ def _declare(lib):
     lib.mcaq_bit_budget_forward.argtypes = [ctypes.POINTER(P), ctypes.POINTER(I), I, Fl, P, P, P]
     lib.mcaq_qat_smask_backward_multi.restype = I
     lib.mcaq_qat_smask_backward_multi.argtypes = [ctypes.POINTER(QatSmaskSeg), I, ctypes.POINTER(BitBudget), P]
+    lib.mcaq_qat_forward_tile_losses.restype = I
+    lib.mcaq_qat_forward_tile_losses.argtypes = [ctypes.POINTER(QatScale), I, ctypes.POINTER(P), ctypes.POINTER(I), I,
+                                                 P, P, ctypes.POINTER(TileLosses), P]
+    lib.mcaq_tile_losses_forward.restype = I
+    lib.mcaq_tile_losses_forward.argtypes = [ctypes.POINTER(P), ctypes.POINTER(I), I, P, P,
+                                             ctypes.POINTER(TileLosses), P]
+    lib.mcaq_qat_smask_backward_tile_losses.restype = I
+    lib.mcaq_qat_smask_backward_tile_losses.argtypes = [ctypes.POINTER(QatSmaskSeg), I, ctypes.POINTER(TileLosses), P]
     lib.mcaq_clip_adamw.restype = I
     lib.mcaq_clip_adamw.argtypes = [ctypes.POINTER(AdamwSeg), I, P, I, P, Fl, P, P, P]
     lib.mcaq_clip_adamw_work_floats.restype = ctypes.c_size_t
@@ -320,7 +335,11 @@ def load_library(path=LIB_PATH):
         raise NativeLibraryMissing(
             "libmcaq_hip.so not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % path)
     import torch  # noqa: F401  (loads torch's libamdhip64 first: one HIP runtime per process)
-    lib = _declare(ctypes.CDLL(path))
+    try:
+        lib = _declare(ctypes.CDLL(path))
+    except AttributeError as e:
+        # an older build of the same ABI version without a later, additive entry
+        raise NativeLibraryMissing("libmcaq_hip.so lacks an entry this package needs: %s (rebuild)" % e) from None
     v = lib.mcaq_abi_version()
     if v != ABI_VERSION:
         raise NativeLibraryMissing("libmcaq_hip.so ABI %d != expected %d (rebuild)" % (v, ABI_VERSION))

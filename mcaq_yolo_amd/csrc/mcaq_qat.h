@@ -22,8 +22,31 @@
 
 namespace mcaq {
 
-// the train step's bit budget riding on the QAT forward launch (nseg = 0: none)
-struct QatBudget { const float* bits[3]; int n[3]; int nseg; float target; float* avg; float* loss; };
+// the train step's bit budget riding on the QAT forward launch (nseg = 0: none);
+// smooth (NULL: not computed): the smoothness term of the same bit maps, segment
+// k a (B, ht[k], wt[k]) map of n[k] tiles with ne[k] = max(1, n_edges_k) as a float
+struct QatBudget {
+  const float* bits[3]; int n[3]; int nseg; float target; float* avg; float* loss;
+  float* smooth; int ht[3], wt[3]; float ne[3];
+};
+
+// the smoothness term (MCAQYOLOLoss.compute_smoothness_loss, models/
+// mcaq_yolo.py:86-107) of one (B, ht, wt) bit map of n tiles, one thread's
+// share: tiles tid, tid + nth, ... in order, per tile |b(below) - b| then
+// |b(right) - b| (the neighbour index clamped to the tile itself where the
+// edge does not exist: no load behind a branch, and that edge adds nothing)
+__device__ __forceinline__ float tile_tv_thread(const float* p, int n, int ht, int wt, int tid, int nth) {
+  const int NT = ht * wt;
+  float s = 0.0f;
+  for (int e = tid; e < n; e += nth) {
+    const int t = e % NT, i = t / wt, j = t - i * wt;
+    const bool dn = i + 1 < ht, rt = j + 1 < wt;
+    const float b = p[e], bd = p[dn ? e + wt : e], br = p[rt ? e + 1 : e];
+    s += dn ? fabsf(bd - b) : 0.0f;
+    s += rt ? fabsf(br - b) : 0.0f;
+  }
+  return s;
+}
 
 struct QatArgs {
   mcaq_qat_scale s[3];
@@ -153,32 +176,86 @@ constexpr int QAT_FUSED_MAXW = 512;
 // workgroup of the QAT forward launch, which reads the same bit maps: per
 // segment 8 loads a thread in flight (clamped index, no load behind a
 // branch), a fixed shuffle tree per wave, the 4 waves summed in order
-__device__ __forceinline__ void qat_budget_block(const QatBudget& B, float* red) {
+// With B.smooth (the smoothness term, tile_tv_thread's sum and order) every
+// segment's two sums share one pass: the neighbour loads are issued with the
+// 8 tile loads, the two shuffle trees run side by side and one pair of
+// barriers serves both, so the term adds no dependent round to this
+// workgroup, which is dispatched last and ends the launch
+template <bool kS>
+__device__ __forceinline__ void qat_budget_sums(const QatBudget& B, float* red) {
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  float total = 0.0f;
+  float total = 0.0f, tvt = 0.0f;
   for (int k = 0; k < B.nseg; ++k) {
     const float* p = k == 0 ? B.bits[0] : (k == 1 ? B.bits[1] : B.bits[2]);
     const int n = k == 0 ? B.n[0] : (k == 1 ? B.n[1] : B.n[2]);
-    float s = 0.0f;
+    const int ht = k == 0 ? B.ht[0] : (k == 1 ? B.ht[1] : B.ht[2]);
+    const int wt = k == 0 ? B.wt[0] : (k == 1 ? B.wt[1] : B.wt[2]);
+    // (tile row, column) of a thread's tiles: one division for its first tile
+    // of a round, then steps of 256 tiles = (dq rows, dj columns) mod the
+    // image's ht x wt grid (dt < NT tiles), with carries
+    const int NT = kS ? ht * wt : 1;
+    const int dt = kS ? 256 % NT : 0, dq = kS ? dt / wt : 0, dj = kS ? dt - dq * wt : 0;
+    float s = 0.0f, tv = 0.0f;
     for (int i0 = tid; i0 < n; i0 += 256 * 8) {
-      float v[8];
+      float v[8], vd[8], vr[8];
+      bool dn[8], rt[8];
+      int t = 0, i = 0, j = 0;
+      if constexpr (kS) {
+        t = i0 % NT; i = t / wt; j = t - i * wt;
+      }
 #pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = p[imin_(i0 + 256 * r, n - 1)];
+      for (int r = 0; r < 8; ++r) {
+        const bool in = i0 + 256 * r < n;
+        const int e = in ? i0 + 256 * r : n - 1;
+        v[r] = p[e];
+        if constexpr (kS) {
+          dn[r] = in && i + 1 < ht;
+          rt[r] = in && j + 1 < wt;
+          vd[r] = p[dn[r] ? e + wt : e];
+          vr[r] = p[rt[r] ? e + 1 : e];
+          t += dt; i += dq; j += dj;
+          if (j >= wt) { j -= wt; ++i; }
+          if (t >= NT) { t -= NT; i -= ht; }
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 8; ++r) s += i0 + 256 * r < n ? v[r] : 0.0f;
+      if constexpr (kS) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          tv += dn[r] ? fabsf(vd[r] - v[r]) : 0.0f;
+          tv += rt[r] ? fabsf(vr[r] - v[r]) : 0.0f;
+        }
+      }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) red[wv] = s;
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o, 64);
+      if constexpr (kS) tv += __shfl_xor(tv, o, 64);
+    }
+    if (lane == 0) {
+      red[wv] = s;
+      if constexpr (kS) red[4 + wv] = tv;
+    }
     __syncthreads();
     total = total + ((red[0] + red[1]) + (red[2] + red[3])) * (1.0f / (float)n);
+    if constexpr (kS) {
+      // S_k = (the sum of |differences| over the edges of map k) / max(1, n_edges_k)
+      const float ne = k == 0 ? B.ne[0] : (k == 1 ? B.ne[1] : B.ne[2]);
+      tvt = tvt + ((red[4] + red[5]) + (red[6] + red[7])) / ne;
+    }
     __syncthreads();
   }
   if (tid == 0) {
     const float avg = total * (1.0f / (float)B.nseg);
     B.avg[0] = avg;
     if (B.loss) B.loss[0] = (avg - B.target) * (avg - B.target);
+    if constexpr (kS) B.smooth[0] = tvt / (float)B.nseg;   // L_smooth = mean_k S_k
   }
+}
+__device__ __forceinline__ void qat_budget_block(const QatBudget& B, float* red) {
+  if (B.smooth) qat_budget_sums<true>(B, red);
+  else qat_budget_sums<false>(B, red);
 }
 
 // kTile: every scale's map is a power-of-two multiple of its tile grid with
@@ -561,21 +638,60 @@ int mcaq_qat_forward(const mcaq_qat_scale* scales, int nscales, hipStream_t stre
   return (int)hipGetLastError();
 }
 
-int mcaq_qat_forward_budget(const mcaq_qat_scale* scales, int nscales, const float* const* bits, const int* n,
-                            int nseg, float target, float* avg, float* loss, hipStream_t stream) {
+// max(1, n_edges) of a (B, ht, wt) bit map as the float the kernels divide by;
+// 0: a non-positive dimension or more tiles than an int indexes
+static float tile_edges(int B, int ht, int wt, int& n) {
+  if (B < 1 || ht < 1 || wt < 1) return 0.0f;
+  const long long nt = (long long)B * ht * wt;
+  if (nt > 0x3fffffffLL) return 0.0f;
+  n = (int)nt;
+  const long long ne = (long long)B * ((long long)(ht - 1) * wt + (long long)ht * (wt - 1));
+  return (float)(ne > 1 ? ne : 1);
+}
+
+// the budget workgroup's arguments; dims (nseg x (B, ht, wt)) with smooth,
+// else the element counts n
+static int qat_budget_args(mcaq::QatBudget& bb, const float* const* bits, const int* n, const int* dims, int nseg,
+                           float target, float* avg, float* loss, float* smooth) {
+  if (!bits || !(dims || n) || nseg < 1 || nseg > 3 || !avg || (smooth && !dims)) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < nseg; ++k) {
+    if (!bits[k]) return (int)hipErrorInvalidValue;
+    bb.bits[k] = bits[k];
+    if (dims) {
+      bb.ne[k] = tile_edges(dims[3 * k], dims[3 * k + 1], dims[3 * k + 2], bb.n[k]);
+      if (bb.ne[k] == 0.0f) return (int)hipErrorInvalidValue;
+      bb.ht[k] = dims[3 * k + 1]; bb.wt[k] = dims[3 * k + 2];
+    } else {
+      if (n[k] < 1) return (int)hipErrorInvalidValue;
+      bb.n[k] = n[k];
+    }
+  }
+  bb.nseg = nseg; bb.target = target; bb.avg = avg; bb.loss = loss; bb.smooth = smooth;
+  return 0;
+}
+
+static int qat_forward_losses(const mcaq_qat_scale* scales, int nscales, const float* const* bits, const int* n,
+                              const int* dims, int nseg, float target, float* avg, float* loss, float* smooth,
+                              hipStream_t stream) {
   mcaq::QatArgs a;
   int blocks;
-  const int e = qat_args(scales, nscales, false, a, blocks);
+  int e = qat_args(scales, nscales, false, a, blocks);
   if (e) return e;
-  if (!bits || !n || nseg < 1 || nseg > 3 || !avg) return (int)hipErrorInvalidValue;
-  for (int k = 0; k < nseg; ++k) {
-    if (!bits[k] || n[k] < 1) return (int)hipErrorInvalidValue;
-    a.bb.bits[k] = bits[k];
-    a.bb.n[k] = n[k];
-  }
-  a.bb.nseg = nseg; a.bb.target = target; a.bb.avg = avg; a.bb.loss = loss;
+  e = qat_budget_args(a.bb, bits, n, dims, nseg, target, avg, loss, smooth);
+  if (e) return e;
   mcaq::qat_launch<false>(scales, nscales, a.units_total + 1, stream, a);
   return (int)hipGetLastError();
+}
+
+int mcaq_qat_forward_budget(const mcaq_qat_scale* scales, int nscales, const float* const* bits, const int* n,
+                            int nseg, float target, float* avg, float* loss, hipStream_t stream) {
+  return qat_forward_losses(scales, nscales, bits, n, nullptr, nseg, target, avg, loss, nullptr, stream);
+}
+
+int mcaq_qat_forward_tile_losses(const mcaq_qat_scale* scales, int nscales, const float* const* bits, const int* dims,
+                                 int nseg, float* avg, float* loss, const mcaq_tile_losses* tl, hipStream_t stream) {
+  if (!tl || !dims) return (int)hipErrorInvalidValue;
+  return qat_forward_losses(scales, nscales, bits, nullptr, dims, nseg, tl->target, avg, loss, tl->smooth, stream);
 }
 
 int mcaq_qat_backward(const mcaq_qat_scale* scales, int nscales, hipStream_t stream) {

@@ -1524,11 +1524,17 @@ struct MaskTrainArgs {
   // slice partials (mcaq_qat_backward with gm = gb = NULL) are folded here -
   // grad m(p) straight into the staged plane, the quantizer's grad_bits in
   // the fold kernel's order - and gbits = (c + grad_bits(quantizer)) +
-  // grad_bits(soft mask), c the bit-budget gradient per tile (bb)
+  // grad_bits(soft mask), c the bit-budget gradient per tile (bb).  With an
+  // upstream gradient of the smoothness term (g_smooth set) the tile constant
+  // is c + s kappa: gbits = ((c + s kappa) + grad_bits(quantizer)) +
+  // grad_bits(soft mask), s = (g_smooth / nscales) / se, kappa the integer
+  // sum of sign(b - b(neighbour)) over the tile's neighbours inside the image
   const float* qwork;
   int qC;
   mcaq_bit_budget bb;
   float rn;              // 1 / (B * ht * wt) of this scale
+  const float* g_smooth; // dL / dL_smooth (device scalar), or NULL: no smoothness term
+  float se;              // max(1, n_edges) of this scale
 };
 
 // LDS bytes of the soft-mask backward of one (H, W, ht, wt) image; stage: + the
@@ -1763,6 +1769,14 @@ __device__ __forceinline__ void mcaq_smask_bwd_body(const MaskTrainArgs& A) {
       if (A.bb.g_loss) dA = dA + A.bb.g_loss[0] * (2.0f * (A.bb.avg[0] - A.bb.target));
       c = (dA * (1.0f / (float)A.bb.nscales)) * A.rn;
     }
+    // the smoothness term's gradient (MCAQYOLOLoss.compute_smoothness_loss,
+    // models/mcaq_yolo.py:86-107: the per-edge mean total variation, averaged
+    // over the scales): s kappa(t), kappa the integer sum of sign(b - b') over
+    // the neighbours b' of tile t inside this image (sign(0) = 0, as abs
+    // differentiates); s once per workgroup
+    const bool has_s = A.g_smooth != nullptr;
+    const float sk = has_s ? (A.g_smooth[0] / (float)A.bb.nscales) / A.se : 0.0f;
+    const float* bimg = A.bits + (size_t)b * NT;
     __syncthreads();
     for (int t = tid; t < NT; t += SM_TH) {
       const int i = t / wt, j = t - i * wt;
@@ -1771,7 +1785,17 @@ __device__ __forceinline__ void mcaq_smask_bwd_body(const MaskTrainArgs& A) {
         g = smask_row_sum4(fcol + i * W, wlo[j], whi[j] + 1, 0.0f);   // 16-byte rows
       else
         for (int w = wlo[j]; w <= whi[j]; ++w) g += fcol[i * W + w];
-      fgb[t] = has_c ? c + g : g;
+      if (has_s) {
+        // a missing neighbour reads the tile itself (clamped index): sign 0
+        const float bv = bimg[t];
+        const float bu = bimg[i > 0 ? t - wt : t], bd = bimg[i + 1 < ht ? t + wt : t];
+        const float bl = bimg[j > 0 ? t - 1 : t], br = bimg[j + 1 < wt ? t + 1 : t];
+        const int kap = ((bv > bu) - (bv < bu)) + ((bv > bd) - (bv < bd)) + ((bv > bl) - (bv < bl)) +
+                        ((bv > br) - (bv < br));
+        fgb[t] = (c + sk * (float)kap) + g;
+      } else {
+        fgb[t] = has_c ? c + g : g;
+      }
     }
   } else if (A.stage) {
     __syncthreads();   // every pooling read of the staged |x| plane is done
@@ -2155,7 +2179,14 @@ __global__ __launch_bounds__(SM_TH) void mcaq_smask_bwd_multi_kernel(TrMulti<Mas
 // per thread a strided sum, then the block's halving tree), their mean, and
 // (avg - target)^2 - deterministic; ATen's CUDA mean reduces in another order
 // (fp32 rounding apart)
-struct BitBudgetArgs { const float* bits[TR_MAXSEG]; int n[TR_MAXSEG]; int nseg; float target; float* avg; float* loss; };
+// smooth (NULL: not computed): the smoothness term of the same maps, L_smooth =
+// mean_k S_k, S_k = (the sum of |differences| over the edges of map k) /
+// max(1, n_edges_k) (MCAQYOLOLoss.compute_smoothness_loss, models/
+// mcaq_yolo.py:86-107), each S_k's sum through the same tree
+struct BitBudgetArgs {
+  const float* bits[TR_MAXSEG]; int n[TR_MAXSEG]; int nseg; float target; float* avg; float* loss;
+  float* smooth; int ht[TR_MAXSEG], wt[TR_MAXSEG]; float ne[TR_MAXSEG];
+};
 __global__ __launch_bounds__(1024) void mcaq_bit_budget_kernel(BitBudgetArgs a) {
   __shared__ float red[1024];
   const int tid = (int)threadIdx.x;
@@ -2177,6 +2208,19 @@ __global__ __launch_bounds__(1024) void mcaq_bit_budget_kernel(BitBudgetArgs a) 
     a.avg[0] = avg;
     if (a.loss) a.loss[0] = (avg - a.target) * (avg - a.target);
   }
+  if (!a.smooth) return;
+  float tv = 0.0f;
+  for (int k = 0; k < a.nseg; ++k) {
+    red[tid] = tile_tv_thread(a.bits[k], a.n[k], a.ht[k], a.wt[k], tid, 1024);
+    __syncthreads();
+    for (int h = 512; h > 0; h >>= 1) {
+      if (tid < h) red[tid] = red[tid] + red[tid + h];
+      __syncthreads();
+    }
+    tv = tv + red[0] / a.ne[k];
+    __syncthreads();
+  }
+  if (tid == 0) a.smooth[0] = tv / (float)a.nseg;
 }
 
 // parameter-gradient reductions of several segments.  chain = 0: segment k
@@ -2945,8 +2989,10 @@ int mcaq_smask_train_backward_multi(const mcaq_smask_seg* segs, int nseg, hipStr
   return (int)hipGetLastError();
 }
 
-int mcaq_qat_smask_backward_multi(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_bit_budget* bb,
-                                  hipStream_t stream) {
+// g_smooth: the upstream gradient of the smoothness term (NULL: none, the
+// values of the launch without the term)
+static int qat_smask_backward_losses(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_bit_budget* bb,
+                                     const float* g_smooth, hipStream_t stream) {
   using namespace mcaq;
   if (!segs || !bb || nseg < 1 || nseg > TR_MAXSEG || bb->nscales < 1 ||
       ((bb->g_avg || bb->g_loss) && !bb->avg))
@@ -2964,6 +3010,10 @@ int mcaq_qat_smask_backward_multi(const mcaq_qat_smask_seg* segs, int nseg, cons
     A.B = g.B; A.H = g.H; A.W = g.W; A.ht = g.ht; A.wt = g.wt; A.accumulate = 0; A.wg0 = wg;
     A.qwork = g.qat_work; A.qC = g.C; A.bb = *bb;
     A.rn = 1.0f / (float)(g.B * g.ht * g.wt);
+    A.g_smooth = g_smooth;
+    int nt;
+    A.se = tile_edges(g.B, g.ht, g.wt, nt);
+    if (A.se == 0.0f) return (int)hipErrorInvalidValue;
     // the |x| plane staged when it fits (16-byte rows of 4); the fold planes always in LDS
     A.stage = (((g.H * g.W) & 3) == 0 && ((uintptr_t)g.absmean & 15) == 0) ? 1 : 0;
     wg += g.B;
@@ -2983,18 +3033,43 @@ int mcaq_qat_smask_backward_multi(const mcaq_qat_smask_seg* segs, int nseg, cons
   return (int)hipGetLastError();
 }
 
-int mcaq_bit_budget_forward(const float* const* bits, const int* n, int nseg, float target, float* avg, float* loss,
-                            hipStream_t stream) {
+int mcaq_qat_smask_backward_multi(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_bit_budget* bb,
+                                  hipStream_t stream) {
+  return qat_smask_backward_losses(segs, nseg, bb, nullptr, stream);
+}
+
+int mcaq_qat_smask_backward_tile_losses(const mcaq_qat_smask_seg* segs, int nseg, const mcaq_tile_losses* tl,
+                                        hipStream_t stream) {
+  if (!tl) return (int)hipErrorInvalidValue;
+  const mcaq_bit_budget bb{tl->avg, tl->g_avg, tl->g_loss, tl->target, tl->nscales};
+  return qat_smask_backward_losses(segs, nseg, &bb, tl->g_smooth, stream);
+}
+
+// dims (nseg x (B, ht, wt)) with smooth, else the element counts n
+static int tile_losses_forward(const float* const* bits, const int* n, const int* dims, int nseg, float target,
+                               float* avg, float* loss, float* smooth, hipStream_t stream) {
   using namespace mcaq;
-  if (!bits || !n || !avg || nseg < 1 || nseg > TR_MAXSEG) return (int)hipErrorInvalidValue;
+  QatBudget q{};
+  const int e = qat_budget_args(q, bits, n, dims, nseg, target, avg, loss, smooth);
+  if (e) return e;
   BitBudgetArgs a{};
   for (int k = 0; k < nseg; ++k) {
-    if (!bits[k] || n[k] < 1) return (int)hipErrorInvalidValue;
-    a.bits[k] = bits[k]; a.n[k] = n[k];
+    a.bits[k] = q.bits[k]; a.n[k] = q.n[k]; a.ht[k] = q.ht[k]; a.wt[k] = q.wt[k]; a.ne[k] = q.ne[k];
   }
-  a.nseg = nseg; a.target = target; a.avg = avg; a.loss = loss;
+  a.nseg = nseg; a.target = target; a.avg = avg; a.loss = loss; a.smooth = smooth;
   hipLaunchKernelGGL(mcaq_bit_budget_kernel, dim3(1), dim3(1024), 0, stream, a);
   return (int)hipGetLastError();
+}
+
+int mcaq_bit_budget_forward(const float* const* bits, const int* n, int nseg, float target, float* avg, float* loss,
+                            hipStream_t stream) {
+  return tile_losses_forward(bits, n, nullptr, nseg, target, avg, loss, nullptr, stream);
+}
+
+int mcaq_tile_losses_forward(const float* const* bits, const int* dims, int nseg, float* avg, float* loss,
+                             const mcaq_tile_losses* tl, hipStream_t stream) {
+  if (!tl || !dims) return (int)hipErrorInvalidValue;
+  return tile_losses_forward(bits, nullptr, dims, nseg, tl->target, avg, loss, tl->smooth, stream);
 }
 
 int mcaq_train_reduce_multi(const mcaq_reduce_seg* segs, int nseg, int chain, hipStream_t stream) {

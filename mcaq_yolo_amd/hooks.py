@@ -41,6 +41,22 @@ MULTI_SCALE_TRAIN = True
 CONCURRENT_TRAIN_SCALES = True
 
 
+def smoothness_of(bit_map):
+    """MCAQYOLOLoss.compute_smoothness_loss (models/mcaq_yolo.py:86-107) as
+    torch ops: for a (B, ht, wt) map (a 2-D map is a batch of one) the sum of
+    |vertical differences| and |horizontal differences| over max(1, n_edges);
+    for a list of maps the mean over the maps."""
+    if isinstance(bit_map, (list, tuple)):
+        losses = [smoothness_of(m) for m in bit_map]
+        return sum(losses) / max(1, len(losses))
+    b = bit_map.float()
+    if b.dim() == 2:
+        b = b.unsqueeze(0)
+    B, ht, wt = b.shape
+    tv = (b[:, 1:, :] - b[:, :-1, :]).abs().sum() + (b[:, :, 1:] - b[:, :, :-1]).abs().sum()
+    return tv / max(1, B * ((ht - 1) * wt + ht * (wt - 1)))
+
+
 class MCAQHooks(nn.Module):
     def __init__(self, grid_size=8, min_bits=2, max_bits=8, bit_mapping="mlp", normalize_complexity=False,
                  device="cuda", indices=DEFAULT_INDICES, half_arithmetic="fp32"):
@@ -148,6 +164,32 @@ class MCAQHooks(nn.Module):
         if b is not None and b["target"] == t:
             return b["loss_bit"]
         return (MCAQHooks.avg_bits(aux) - t) ** 2
+
+    @staticmethod
+    def smoothness_loss(aux):
+        """MCAQYOLOLoss.compute_smoothness_loss (models/mcaq_yolo.py:86-107):
+        the per-edge mean total variation of every scale's bit map, averaged
+        over the scales.  aux: a forward's aux records, or what the reference
+        takes (one 2-D / 3-D bit map, or a list of maps).  After a multi-scale
+        train step with train_step.FUSED_SMOOTHNESS: the value its bit-budget
+        workgroup computed, whose gradient is folded into that step's
+        backward launch; otherwise smoothness_of(...) (torch ops)."""
+        if torch.is_tensor(aux):
+            return smoothness_of(aux)
+        aux = list(aux)
+        if not all(isinstance(a, dict) for a in aux):
+            return smoothness_of(aux)
+        b = MCAQHooks._budget(aux)
+        if b is not None and train_step.FUSED_SMOOTHNESS and b.get("loss_smooth") is not None:
+            return b["loss_smooth"]
+        return smoothness_of([a["bit_map"] for a in aux])
+
+    def tile_losses(self, aux, target_bits=None):
+        """The tile-domain inputs of the QAT objective (Eq. 20) under the
+        reference's loss_dict names: avg_bits, loss_bit (at target_bits,
+        default self.target_bits) and loss_smooth."""
+        return {"avg_bits": MCAQHooks.avg_bits(aux), "loss_bit": self.bit_budget_loss(aux, target_bits),
+                "loss_smooth": MCAQHooks.smoothness_loss(aux)}
 
     # -- the hook body (models/mcaq_yolo.py:409-455)
     def make_hook(self, layer_idx):

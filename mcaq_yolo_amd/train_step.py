@@ -768,6 +768,18 @@ class _SoftMaskMulti(torch.autograd.Function):
 # _SoftMaskMulti / _QATMulti nodes and avg_bits as torch ops.
 FUSED_MASK_QAT = True
 
+# The smoothness term of the QAT loss (MCAQYOLOLoss.compute_smoothness_loss,
+# models/mcaq_yolo.py:86-107: the per-edge mean total variation of every bit
+# map, averaged over the scales) rides on the same node: its value comes from
+# the bit-budget workgroup of the quantizer's forward launch and its gradient
+# is the tile constant s kappa that the fused backward adds beside the bit
+# budget's c - no launch of its own and still ONE gradient per bit map, instead
+# of the strided differences / abs / sums and their autograd mirror per scale.
+# False: the node computes no smoothness value (the launches and entries of
+# the step before the term existed) and MCAQHooks.smoothness_loss is torch
+# ops on the step's bit maps - the equivalence oracle.  Read at call time.
+FUSED_SMOOTHNESS = True
+
 # fp16 / bf16 feature maps (the maps of an autocast training step) are read by
 # pass 1 and by the QAT quantizer as they are, saved for the backward as they
 # are, and receive their gradient in their own dtype (mcaq_stats_scale.dtype,
@@ -794,7 +806,11 @@ class _MaskQuantMulti(torch.autograd.Function):
     soft-mask backward + bit-budget gradient (one launch), the soft-mask
     parameter reduction (one launch).  Per tile the bit-map gradient is
     (c + grad_bits(quantizer)) + grad_bits(soft mask), the order autograd
-    sums them in the per-scale step."""
+    sums them in the per-scale step.  FUSED_SMOOTHNESS: one more output after
+    avg and loss, L_smooth (models/mcaq_yolo.py:86-107) from the bit-budget
+    workgroup; with its gradient present the tile constant is c + s kappa,
+    ((c + s kappa) + grad_bits(quantizer)) + grad_bits(soft mask); with it
+    absent (None: a null pointer) the values without the term, bit for bit."""
 
     @staticmethod
     def forward(ctx, mods, n, target, *args):
@@ -842,13 +858,23 @@ class _MaskQuantMulti(torch.autograd.Function):
         avg = torch.empty((), device=dev)
         loss = torch.empty((), device=dev)
         bp = (abi.P * n)(*[_p(b) for b in bf])
-        bn = (abi.I * n)(*[b.numel() for b in bf])
+        ctx.fused_smooth = bool(FUSED_SMOOTHNESS)
+        smooth = None
         # the quantizer and the bit budget (one extra workgroup) in one launch
-        abi.check(L.mcaq_qat_forward_budget(arr, n, bp, bn, n, float(target), _p(avg), _p(loss), st),
-                  "mcaq_qat_forward_budget")
+        if ctx.fused_smooth:
+            # ... and the smoothness term from the same workgroup
+            smooth = torch.empty((), device=dev)
+            dims = (abi.I * (3 * n))(*[d for b in bf for d in b.shape])
+            tl = abi.TileLosses(None, None, None, float(target), n, _p(smooth), None)
+            abi.check(L.mcaq_qat_forward_tile_losses(arr, n, bp, dims, n, _p(avg), _p(loss), ctypes.byref(tl), st),
+                      "mcaq_qat_forward_tile_losses")
+        else:
+            bn = (abi.I * n)(*[b.numel() for b in bf])
+            abi.check(L.mcaq_qat_forward_budget(arr, n, bp, bn, n, float(target), _p(avg), _p(loss), st),
+                      "mcaq_qat_forward_budget")
         ctx.mods, ctx.n, ctx.target = mods, n, float(target)
         ctx.save_for_backward(*xs, *bf, *ms, *absmeans, *mins, *maxs, avg)
-        return tuple(ys) + (avg, loss)
+        return tuple(ys) + (avg, loss, smooth)
 
     @staticmethod
     def backward(ctx, *grads):
@@ -856,7 +882,7 @@ class _MaskQuantMulti(torch.autograd.Function):
         sv = ctx.saved_tensors
         xs, bits, ms, absmeans, mins, maxs = (sv[k * n:(k + 1) * n] for k in range(6))
         avg = sv[6 * n]
-        gys, g_avg, g_loss = grads[:n], grads[n], grads[n + 1]
+        gys, g_avg, g_loss, g_smooth = grads[:n], grads[n], grads[n + 1], grads[n + 2]
         L = abi.lib()
         st = _stream()
         arr = (abi.QatScale * n)()
@@ -897,8 +923,15 @@ class _MaskQuantMulti(torch.autograd.Function):
         abi.check(L.mcaq_qat_backward(arr, n, st), "mcaq_qat_backward")
         ga = _f32c(g_avg) if g_avg is not None else None
         gl = _f32c(g_loss) if g_loss is not None else None
-        bb = abi.BitBudget(_p(avg), _p(ga), _p(gl), ctx.target, n)
-        abi.check(L.mcaq_qat_smask_backward_multi(segs, n, ctypes.byref(bb), st), "mcaq_qat_smask_backward_multi")
+        if ctx.fused_smooth:
+            gs = _f32c(g_smooth) if g_smooth is not None else None     # None: a null pointer, no smoothness term
+            tl = abi.TileLosses(_p(avg), _p(ga), _p(gl), ctx.target, n, None, _p(gs))
+            abi.check(L.mcaq_qat_smask_backward_tile_losses(segs, n, ctypes.byref(tl), st),
+                      "mcaq_qat_smask_backward_tile_losses")
+        else:
+            bb = abi.BitBudget(_p(avg), _p(ga), _p(gl), ctx.target, n)
+            abi.check(L.mcaq_qat_smask_backward_multi(segs, n, ctypes.byref(bb), st),
+                      "mcaq_qat_smask_backward_multi")
         # every net's gradients straight into its _GradSink (their .grad), the
         # reduction deferred to the mapper's backward launch; otherwise
         # reduced here and handed to autograd
@@ -1111,7 +1144,9 @@ def _quantize_multi(hooks, feats, state, n, idxs, xs, box, cs, bits, qs, per_qua
                                         *feats, *mins, *maxs, *[p for q in qs for p in q.soft_mask.net.parameters()])
         finally:
             _flush_ema()         # normally taken by the soft-mask launch
-        ys, budget = list(res[:n]), {"avg_bits": res[n], "loss_bit": res[n + 1], "target": target, "bits": bits}
+        # loss_smooth: None when the step ran with FUSED_SMOOTHNESS off
+        ys, budget = list(res[:n]), {"avg_bits": res[n], "loss_bit": res[n + 1], "target": target, "bits": bits,
+                                     "loss_smooth": res[n + 2]}
         for i in range(n):
             state.setdefault("aux", []).append({"layer": idxs[i], "complexity": cs[i], "bit_map": bits[i],
                                                 "features_q": ys[i], "_bit_budget": budget})
