@@ -6,9 +6,13 @@
 // torchvision's CPU `nms` kernel.  Restated from their published algorithm:
 //
 //   per image: candidates = anchors with max class score > conf_thres
-//              (score = max, cls = first argmax); box xywh -> xyxy
+//              (score = max, cls = first argmax; a NaN in any class score
+//              makes the max NaN, as `amax` has it, so that anchor is no
+//              candidate whichever class carries the NaN); box xywh -> xyxy
 //              (xy -/+ wh/2); order by score descending (stable: anchor
-//              index ascending on ties); keep the first max_nms;
+//              index ascending on ties; +0 and -0 scores tie: the score is
+//              canonicalised to +0 before it becomes a sort key); keep the
+//              first max_nms;
 //              boxes offset by cls * max_wh (0 when agnostic);
 //              greedy: a candidate is kept unless IoU(kept, cand) > iou_thres
 //              for an earlier kept box, IoU = inter / (area_k + area_c - inter)
@@ -101,19 +105,25 @@ __global__ __launch_bounds__(NMS_SCAN_THREADS) void mcaq_nms_scan_kernel(NmsArgs
   int bj = 0;
   if (ai < N) {
     best = P[(size_t)4 * N + ai];
+    bool nan = best != best;             // amax propagates NaN: such an anchor is dropped
     int c = 1;
     for (; c + 8 <= a.nc; c += 8) {      // 8 class rows in flight, compared in class order
       float v[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = P[(size_t)(4 + c + k) * N + ai];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) if (v[k] > best) { best = v[k]; bj = c + k; }
+      for (int k = 0; k < 8; ++k) {
+        nan |= v[k] != v[k];
+        if (v[k] > best) { best = v[k]; bj = c + k; }
+      }
     }
     for (; c < a.nc; ++c) {
       const float v = P[(size_t)(4 + c) * N + ai];
+      nan |= v != v;
       if (v > best) { best = v; bj = c; }
     }
-    cand = best > a.conf;
+    best += 0.0f;                        // -0 -> +0: zeros of either sign tie in the sort
+    cand = !nan && best > a.conf;
   }
   // one atomic per wave: slots in lane order
   const unsigned long long mask = __ballot(cand);
@@ -294,7 +304,8 @@ int mcaq_nms(const float* pred, int B, int no, int N, int nc, float conf_thres, 
   if (B < 0 || nc < 1 || no != 4 + nc || N < 0 || N > (1 << 30) || max_det < 1 || max_nms < 1)
     return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
-  if (!pred || !out || !counts || !work) return (int)hipErrorInvalidValue;
+  // N == 0: an empty prediction has no storage (counts 0, zero rows)
+  if ((!pred && N > 0) || !out || !counts || !work) return (int)hipErrorInvalidValue;
   mcaq::NmsArgs a;
   a.pred = pred; a.out = out; a.counts = counts; a.kept = work;
   a.cls = reinterpret_cast<int*>(work + (size_t)B * max_det * 8);

@@ -13,6 +13,10 @@ Restates, in numpy fp32 with the reference's op order:
   * torchvision's CPU `nms` kernel (greedy, stable score-descending order,
     IoU = inter / (area_i + area_j - inter) in fp32, `> iou_threshold` in
     double) - torchvision is absent here as well.
+Non-finite and signed-zero scores follow from those two: `amax` propagates
+NaN, so an anchor with a NaN in ANY class score has a NaN maximum, fails
+`> conf_thres` and is no candidate (`cls.max(1)` below does the same); +0.0 and
+-0.0 scores compare equal, so the stable sort orders them by anchor index.
 Parity status: UNPINNED against ultralytics/torchvision (neither is
 installed and the reference holds no NMS fixtures); the GPU kernel is checked
 bit-exactly against this restatement.

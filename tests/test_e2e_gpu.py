@@ -90,7 +90,7 @@ def test_nms_list_api_and_errors():
 @pytest.mark.parametrize("B,nc,N,seed,kw", [
     (2, 80, 33600, 12, {}),                                   # 1280x1280 head: > 16,384 candidates, global keys
     (1, 4, 33600, 13, {"conf": 0.0, "max_det": 1000}),        # every anchor a candidate, max_nms = 30000 cut
-    (2, 80, 16385, 14, {"conf": 0.0, "max_det": 1000}),       # every anchor a candidate: one past the LDS keys
+    (2, 80, 16385, 14, {"conf": 0.0, "max_det": 1000}),       # every anchor a candidate: one past a power of two, global sort padded to 32768
 ])
 def test_nms_large_inputs(B, nc, N, seed, kw):
     """Anchor counts beyond the LDS key array (NMS_LDS_KEYS): candidates are
