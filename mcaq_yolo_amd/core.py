@@ -55,6 +55,25 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _ptr_struct(cls, params):
+    """An abi parameter struct (CmlpParams, SmaskParams) of the tensors' device pointers, in field order."""
+    return cls(*[_p(p.detach()) for p in params])
+
+
+def _mapper_params(net):
+    """abi.MapperParams of a mapping network (Linear, BatchNorm1d, ReLU x 3, Linear)."""
+    q = abi.MapperParams()
+    for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4"),
+                    (net[0].weight, net[0].bias, net[3].weight, net[3].bias, net[6].weight, net[6].bias,
+                     net[9].weight, net[9].bias)):
+        setattr(q, k, _p(t.detach()))
+    for i, bn in enumerate((net[1], net[4], net[7]), 1):
+        for k, t in (("g", bn.weight), ("be", bn.bias), ("rm", bn.running_mean), ("rv", bn.running_var),
+                     ("nbt", bn.num_batches_tracked)):
+            setattr(q, "%s%d" % (k, i), _p(t.detach()) if t is not None else None)
+    return q
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -1128,7 +1147,7 @@ class _HeadTrainFn(torch.autograd.Function):
         B, ht, wt = craw.shape
         n = B * ht * wt
         L = abi.lib()
-        q = abi.CmlpParams(*[_p(p.detach()) for p in params])
+        q = _ptr_struct(abi.CmlpParams, params)
         gcraw = torch.empty(n, device=craw.device)
         mod_params = list(ctx.mod.complexity_mlp.parameters())
         sink = ctx.mod._gsink.target(mod_params) if len(mod_params) == len(params) else None
@@ -1275,15 +1294,7 @@ class _MapperTrainFn(torch.autograd.Function):
         n = cf.numel()
         L = abi.lib()
         bns = [net[i] for i in (1, 4, 7)]
-        q = abi.MapperParams()
-        for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4"),
-                        (net[0].weight, net[0].bias, net[3].weight, net[3].bias, net[6].weight, net[6].bias,
-                         net[9].weight, net[9].bias)):
-            setattr(q, k, _p(t.detach()))
-        for i, bn in enumerate(bns, 1):
-            for k, t in (("g", bn.weight), ("be", bn.bias), ("rm", bn.running_mean), ("rv", bn.running_var),
-                         ("nbt", bn.num_batches_tracked)):
-                setattr(q, "%s%d" % (k, i), _p(t.detach()) if t is not None else None)
+        q = _mapper_params(net)
         T = max(float(temperature), 0.1) if temperature is not None else 0.0
         work = torch.empty(L.mcaq_mapper_work_floats(n), device=c.device)
         bits = torch.empty(n, device=c.device)
@@ -1408,7 +1419,7 @@ def _smask_backward_fused(ctx, mod, bit_map, absmean, gm, params):
     B, H, W = absmean.shape
     _, ht, wt = bit_map.shape
     L = abi.lib()
-    q = abi.SmaskParams(*[_p(p.detach()) for p in params])
+    q = _ptr_struct(abi.SmaskParams, params)
     gb = torch.empty(B, ht, wt, device=absmean.device)
     gflat = torch.empty(_SM_SIZE, device=absmean.device)
     gpart = torch.empty(L.mcaq_smask_gpart_floats(B), device=absmean.device)

@@ -115,15 +115,6 @@ __device__ __forceinline__ float tr_ordered_sum(const float* __restrict__ part, 
   return s;
 }
 
-// out[e] (+)= sum_w part[w * stride + e], e < count, w in order
-__global__ __launch_bounds__(256) void mcaq_tr_reduce_kernel(const float* __restrict__ part, int nwg, int stride,
-                                                             int count, float* __restrict__ out, int accumulate) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= count) return;
-  const float s = tr_ordered_sum(part, nwg, stride, e);
-  out[e] = accumulate ? out[e] + s : s;
-}
-
 // ============================================================================
 // bit mapper, train mode
 // ============================================================================
@@ -685,12 +676,6 @@ __device__ __forceinline__ void mapper_fwd_stage(const MapperTrainArgs& A, MapFw
   }
 }
 
-template <int S>
-__global__ __launch_bounds__(MTH) void mcaq_mapper_fwd_kernel(MapperTrainArgs A) {
-  __shared__ MapFwdLds L;
-  mapper_fwd_stage<S>(A, L);
-}
-
 // grid-wide barrier of a launch whose workgroups are all resident (the mapper
 // grids are n / 64 <= a few hundred 512-thread workgroups): every wave
 // releases its writes at agent scope, one thread counts in and waits, every
@@ -1125,12 +1110,6 @@ __global__ __launch_bounds__(64) void mcaq_mapper_reduce_kernel(const float* wor
   }
 }
 
-template <int S>
-__global__ __launch_bounds__(MTH) void mcaq_mapper_bwd_kernel(MapperTrainArgs A) {
-  __shared__ MapBwdLds L;
-  mapper_bwd_stage<S>(A, L);
-}
-
 // the four backward stages and the parameter reduction in one launch
 __global__ __launch_bounds__(MTH) void mcaq_mapper_bwd_coop_kernel(MapperTrainArgs A, unsigned* bar, float* gparams,
                                                                    int accumulate) {
@@ -1270,7 +1249,6 @@ __device__ __forceinline__ void mcaq_bilateral_bwd_body(const HeadTrainArgs& A) 
   }
   TSTAMP(60);
 }
-__global__ __launch_bounds__(BL_TH) void mcaq_bilateral_bwd_kernel(HeadTrainArgs A) { mcaq_bilateral_bwd_body(A); }
 
 // complexity MLP backward (Linear(8,64)-LN-ReLU-Linear(64,32)-LN-ReLU-
 // Linear(32,1)-sigmoid, recomputed): 64 tiles per workgroup, one per lane;
@@ -1502,7 +1480,6 @@ __device__ __forceinline__ void mcaq_cmlp_bwd_body(const HeadTrainArgs& A, mapx_
   }
   TSTAMP(22);
 }
-__global__ __launch_bounds__(64 * CB_NW) void mcaq_cmlp_bwd_kernel(HeadTrainArgs A) { mcaq_cmlp_bwd_body(A); }
 
 // ============================================================================
 // soft mask backward (one workgroup per image)
@@ -2016,7 +1993,6 @@ __device__ __forceinline__ void mcaq_smask_bwd_body(const MaskTrainArgs& A) {
   }
   TSTAMP(40);
 }
-__global__ __launch_bounds__(SM_TH) void mcaq_smask_bwd_kernel(MaskTrainArgs A) { mcaq_smask_bwd_body(A); }
 
 // ---- device packing of parameter blobs --------------------------------------
 // out[seg.dst + i] for every segment: mode 0 copies n floats from src; mode 1
@@ -2073,10 +2049,12 @@ __global__ __launch_bounds__(256, MCAQ_STATS_MINW) void mcaq_stats_pack_kernel(S
 // ============================================================================
 // ============================================================================
 // multi-segment launches: the hook scales of one train step (each its own
-// tensors, the same parameters) in ONE launch per stage.  A segment is the
-// single-scale launch's argument block with wg0 = its first workgroup; every
-// workgroup runs the single-scale body of its segment, so the values are those
-// of the per-scale launches.  Single-stream HIP graphs of the QAT step then
+// tensors, the same parameters) in ONE launch per stage.  A segment is one
+// scale's argument block with wg0 = its first workgroup; every workgroup runs
+// the body of its segment.  The single-scale entries are the one-segment case
+// (nseg = 1, wg0 = 0) of the same kernels and launchers, so the values of a
+// multi-segment launch are those of the per-scale launches by construction.
+// Single-stream HIP graphs of the QAT step then
 // carry a third of the kernel nodes (graph replay issues a multi-stream graph
 // node by node: tools/probe/graph_replay_probe.py).
 // ============================================================================
@@ -2224,8 +2202,8 @@ __global__ __launch_bounds__(1024) void mcaq_bit_budget_kernel(BitBudgetArgs a) 
 }
 
 // parameter-gradient reductions of several segments.  chain = 0: segment k
-// (blockIdx.y) reduces its partials into its own output, as
-// mcaq_tr_reduce_kernel; chain = 1: every segment into segment 0's output, in
+// (blockIdx.y) reduces its partials into its own output, out[e] (+)= sum_w
+// part[w * stride + e]; chain = 1: every segment into segment 0's output, in
 // segment order - v = s0 (+ out if accumulate), v += s1, v += s2 - the values
 // one reduction launch per segment leaves (the first with `accumulate`, the
 // others accumulating)
@@ -2366,6 +2344,172 @@ __global__ __launch_bounds__(BL_TH) void mcaq_bilateral_bwd_ride_kernel(TrMulti<
   mcaq_bilateral_bwd_body(tr_seg(M));
 }
 
+// ============================================================================
+// launcher layer: every argument block is filled and validated in one place;
+// the single-scale C entries below are its one-segment case
+// ============================================================================
+namespace mcaq {
+
+constexpr int TR_LDS_MAX = 160 * 1024 - 1024;   // dynamic LDS a train kernel may be given
+constexpr size_t CMLP_LDS = (size_t)(TR_TPB * CB_ST + CB_NW * TR_TPB + 4096) * sizeof(float);
+
+// the dynamic-LDS limit of `kernel`, set once per kernel
+static int tr_lds_attr(const void* kernel, int bytes) {
+  static const void* done[8];
+  static int ndone = 0;
+  for (int i = 0; i < ndone; ++i)
+    if (done[i] == kernel) return 0;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return (int)e;
+  if (ndone < 8) done[ndone++] = kernel;
+  return 0;
+}
+
+// the mapper's segments of one launch set -> M; returns the workgroup count,
+// or -1 (refused).  bwd: the backward's tensors (c, gbits, gc, gpart, work)
+// instead of the forward's (c, bits, work).  Sharded stages (world > 0): one
+// pointer per segment in gathered (forward) or gsums and gathered1 (backward).
+static int mapper_segs(TrMulti<MapperTrainArgs>& M, bool bwd, const mcaq_mapper_params* P, const mcaq_mapper_seg* segs,
+                       int nseg, float min_bits, float max_bits, float temperature, float momentum = 0.0f,
+                       int round_bits = 0, int update_stats = 0, int world = 0, const float* const* gathered = nullptr,
+                       const float* const* gsums = nullptr, const float* const* gathered1 = nullptr) {
+  // one launch per stage for every segment: several segments updating the
+  // shared running statistics in-kernel would race (update_stats 1)
+  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || (nseg > 1 && update_stats == 1)) return -1;
+  int wg = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const mcaq_mapper_seg& g = segs[k];
+    if (!g.c || !g.work || g.n < 1 || (bwd ? (!g.gbits || !g.gc || !g.gpart) : !g.bits)) return -1;
+    if (world > 0 && (bwd ? (!gsums[k] || !gathered1[k]) : !gathered[k])) return -1;
+    MapperTrainArgs& A = M.s[k];
+    A.P = *P; A.c = g.c; A.work = g.work; A.n = g.n; A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
+    if (bwd) { A.gbits = g.gbits; A.gc = g.gc; A.gpart = g.gpart; }
+    else A.bits = g.bits;
+    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
+    A.round_bits = round_bits; A.update_stats = update_stats; A.wg0 = wg;
+    if (world > 0) {
+      if (bwd) { A.gbsum = gsums[k]; A.gstat1 = gathered1[k]; }
+      else A.gstat = gathered[k];
+      A.gworld = world;
+    }
+    wg += A.nwg;
+  }
+  M.nseg = nseg;
+  return wg;
+}
+
+static void launch_mapper_fwd_stage(int stage, int grid, hipStream_t stream, const TrMulti<MapperTrainArgs>& M) {
+  const dim3 g(grid), t(MTH);
+  switch (stage) {
+    case 1: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<1>, g, t, 0, stream, M); break;
+    case 2: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<2>, g, t, 0, stream, M); break;
+    case 3: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<3>, g, t, 0, stream, M); break;
+    default: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<4>, g, t, 0, stream, M); break;
+  }
+}
+
+static void launch_mapper_bwd_stage(int stage, int grid, hipStream_t stream, const TrMulti<MapperTrainArgs>& M) {
+  const dim3 g(grid), t(MTH);
+  switch (stage) {
+    case 4: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<4>, g, t, 0, stream, M); break;
+    case 3: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<3>, g, t, 0, stream, M); break;
+    case 2: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<2>, g, t, 0, stream, M); break;
+    default: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<1>, g, t, 0, stream, M); break;
+  }
+}
+
+// rsegs -> R (nr = 0: none); false: refused.  chain: every segment sums into
+// segment 0's output, so only that `out` is required; else each segment needs
+// its own.  same_count: every segment's count must equal segment 0's.
+static bool reduce_segs(TrMulti<TrReduceSeg>& R, const mcaq_reduce_seg* rsegs, int nr, bool chain, bool same_count) {
+  if (nr < 0 || nr > TR_MAXSEG || (nr > 0 && !rsegs)) return false;
+  for (int k = 0; k < nr; ++k) {
+    const mcaq_reduce_seg& g = rsegs[k];
+    if (!g.part || (!g.out && !(chain && k > 0)) || g.nparts < 1 || g.stride < g.count || g.count < 1 ||
+        (same_count && g.count != rsegs[0].count))
+      return false;
+    R.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
+  }
+  R.nseg = nr;
+  return true;
+}
+
+// out (+)= the sum of one launch's `nparts` parameter partials of `count`
+// floats, in workgroup order: a one-segment mcaq_train_reduce_multi
+static int reduce_one(const float* part, int nparts, int count, float* out, int accumulate, hipStream_t stream) {
+  const mcaq_reduce_seg r{part, out, nparts, count, count, accumulate ? 1 : 0, 0.0f};
+  return mcaq_train_reduce_multi(&r, 1, 0, stream);
+}
+
+// the analyzer head's segments: Mb for the bilateral launch (wb workgroups,
+// one per image, lb bytes of LDS), Mc for the complexity MLP's (wc
+// workgroups of 64 tiles)
+struct HeadLaunch {
+  TrMulti<HeadTrainArgs> Mb, Mc;
+  int wb, wc;
+  size_t lb;
+};
+static bool head_segs(HeadLaunch& H, const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg) {
+  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG) return false;
+  H.wb = H.wc = 0;
+  H.lb = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const mcaq_head_seg& g = segs[k];
+    if (!g.phi || !g.craw || !g.gC || !g.gcraw || !g.gpart || g.B < 1 || g.ht < 1 || g.wt < 1) return false;
+    HeadTrainArgs A{};
+    A.P = *P; A.phi = g.phi; A.craw = g.craw; A.gC = g.gC; A.gcraw = g.gcraw; A.gpart = g.gpart;
+    A.B = g.B; A.ht = g.ht; A.wt = g.wt; A.n = g.B * g.ht * g.wt; A.nwg = (A.n + TR_TPB - 1) / TR_TPB;
+    const size_t l = (size_t)53 * g.ht * g.wt * sizeof(float);
+    if (l > (size_t)TR_LDS_MAX) return false;
+    H.lb = l > H.lb ? l : H.lb;
+    H.Mb.s[k] = A; H.Mb.s[k].wg0 = H.wb; H.wb += A.B;      // bilateral: one workgroup per image
+    H.Mc.s[k] = A; H.Mc.s[k].wg0 = H.wc; H.wc += A.nwg;    // MLP: 64 tiles per workgroup
+  }
+  H.Mb.nseg = H.Mc.nseg = nseg;
+  return true;
+}
+
+// the bilateral launch of H, a chain reduction R riding along as extra
+// workgroups when it has segments
+static int launch_bilateral_bwd(const HeadLaunch& H, const TrMulti<TrReduceSeg>& R, hipStream_t stream) {
+  const void* k = R.nseg > 0 ? (const void*)mcaq_bilateral_bwd_ride_kernel : (const void*)mcaq_bilateral_bwd_multi_kernel;
+  const int e = tr_lds_attr(k, TR_LDS_MAX);
+  if (e) return e;
+  if (R.nseg > 0) {
+    const int rw = (R.s[0].count + BL_TH - 1) / BL_TH;
+    hipLaunchKernelGGL(mcaq_bilateral_bwd_ride_kernel, dim3(H.wb + rw), dim3(BL_TH), H.lb, stream, H.Mb, R, H.wb);
+  } else {
+    hipLaunchKernelGGL(mcaq_bilateral_bwd_multi_kernel, dim3(H.wb), dim3(BL_TH), H.lb, stream, H.Mb);
+  }
+  return 0;
+}
+
+// the soft masks' segments -> M, lb = the launch's LDS bytes; returns the
+// workgroup count (one per image), or -1 (refused)
+static int smask_segs(TrMulti<MaskTrainArgs>& M, const mcaq_smask_seg* segs, int nseg, size_t& lb) {
+  if (!segs || nseg < 1 || nseg > TR_MAXSEG) return -1;
+  int wg = 0;
+  lb = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const mcaq_smask_seg& g = segs[k];
+    if (!g.bits || !g.absmean || !g.gm || !g.gbits || !g.gpart || g.B < 1 || g.ht < 1 || g.wt < 1 || g.H < g.ht ||
+        g.W < g.wt)
+      return -1;
+    MaskTrainArgs& A = M.s[k];
+    A.P = g.P; A.bits = g.bits; A.absmean = g.absmean; A.gm = g.gm; A.gbits = g.gbits; A.gpart = g.gpart;
+    A.B = g.B; A.H = g.H; A.W = g.W; A.ht = g.ht; A.wt = g.wt; A.accumulate = g.accumulate; A.wg0 = wg;
+    A.stage = smask_stage_ok(g.absmean, g.gm, g.H, g.W, g.ht, g.wt) ? 1 : 0;
+    wg += g.B;
+    const size_t l = smask_lds_bytes(g.H, g.W, g.ht, g.wt, A.stage != 0);
+    if (l > (size_t)TR_LDS_MAX) return -1;   // m(p) gradient of one image staged in LDS
+    lb = l > lb ? l : lb;
+  }
+  M.nseg = nseg;
+  return wg;
+}
+
+}  // namespace mcaq
+
 extern "C" {
 
 size_t mcaq_mapper_work_floats(int n) { return mcaq::mapper_work_floats(n); }
@@ -2374,20 +2518,15 @@ int mcaq_mapper_train_forward(const mcaq_mapper_params* P, const float* c, int n
                               float temperature, float momentum, int round_bits, int update_stats, float* bits,
                               float* work, unsigned* grid_sync, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !c || !bits || !work || n < 1) return (int)hipErrorInvalidValue;
-  MapperTrainArgs A{};
-  A.P = *P; A.c = c; A.bits = bits; A.work = work; A.n = n; A.nwg = (n + TR_TPB - 1) / TR_TPB;
-  A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
-  A.round_bits = round_bits; A.update_stats = update_stats;
-  const dim3 g(A.nwg), t(MTH);
-  if (grid_sync && A.nwg <= MAPPER_COOP_MAX_WG) {
-    hipLaunchKernelGGL(mcaq_mapper_fwd_coop_kernel, g, t, 0, stream, A, grid_sync);
+  const mcaq_mapper_seg g{c, bits, work, nullptr, nullptr, nullptr, n};
+  TrMulti<MapperTrainArgs> M{};
+  const int wg = mapper_segs(M, false, P, &g, 1, min_bits, max_bits, temperature, momentum, round_bits, update_stats);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  if (grid_sync && wg <= MAPPER_COOP_MAX_WG) {
+    hipLaunchKernelGGL(mcaq_mapper_fwd_coop_kernel, dim3(wg), dim3(MTH), 0, stream, M.s[0], grid_sync);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<1>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<2>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<3>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<4>, g, t, 0, stream, A);
+  for (int st = 1; st <= 4; ++st) launch_mapper_fwd_stage(st, wg, stream, M);
   return (int)hipGetLastError();
 }
 
@@ -2396,24 +2535,19 @@ int mcaq_mapper_train_backward(const mcaq_mapper_params* P, const float* c, int 
                                float* gparams, float* gpart, int accumulate, unsigned* grid_sync,
                                hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !c || !gbits || !gc || !gpart || !work || n < 1 || (!gparams && grid_sync)) return (int)hipErrorInvalidValue;
-  MapperTrainArgs A{};
-  A.P = *P; A.c = c; A.gbits = gbits; A.gc = gc; A.work = work; A.gpart = gpart; A.n = n;
-  A.nwg = (n + TR_TPB - 1) / TR_TPB;
-  A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature;
-  const dim3 g(A.nwg), t(MTH);
-  if (grid_sync && A.nwg <= MAPPER_COOP_MAX_WG) {
-    hipLaunchKernelGGL(mcaq_mapper_bwd_coop_kernel, g, t, 0, stream, A, grid_sync, gparams, accumulate ? 1 : 0);
+  if (!gparams && grid_sync) return (int)hipErrorInvalidValue;
+  const mcaq_mapper_seg g{c, nullptr, work, gbits, gc, gpart, n};
+  TrMulti<MapperTrainArgs> M{};
+  const int wg = mapper_segs(M, true, P, &g, 1, min_bits, max_bits, temperature);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  if (grid_sync && wg <= MAPPER_COOP_MAX_WG) {
+    hipLaunchKernelGGL(mcaq_mapper_bwd_coop_kernel, dim3(wg), dim3(MTH), 0, stream, M.s[0], grid_sync, gparams,
+                       accumulate ? 1 : 0);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<4>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<3>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<2>, g, t, 0, stream, A);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<1>, g, t, 0, stream, A);
-  if (gparams)   // NULL: the caller reduces gpart (mcaq_mapper_train_grad_reduce)
-    hipLaunchKernelGGL(mcaq_tr_reduce_kernel, dim3((MG_SIZE + 255) / 256), dim3(256), 0, stream, (const float*)gpart,
-                       A.nwg, (int)MG_SIZE, (int)MG_SIZE, gparams, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
+  for (int st = 4; st >= 1; --st) launch_mapper_bwd_stage(st, wg, stream, M);
+  if (!gparams) return (int)hipGetLastError();   // the caller reduces gpart (mcaq_mapper_train_grad_reduce)
+  return reduce_one(gpart, wg, MG_SIZE, gparams, accumulate, stream);
 }
 
 int mcaq_mapper_running_update(const mcaq_mapper_params* P, const float* const* works, const int* ns, int count,
@@ -2511,45 +2645,18 @@ int mcaq_mapper_train_forward_stage(const mcaq_mapper_params* P, const float* c,
                                     float max_bits, float temperature, float momentum, int round_bits,
                                     int update_stats, float* bits, float* work, int stage, const float* gathered,
                                     int world, hipStream_t stream) {
-  using namespace mcaq;
-  if (!P || !c || !bits || !work || n < 1 || stage < 1 || stage > 4 || world < 1 || (stage >= 2 && !gathered))
-    return (int)hipErrorInvalidValue;
-  MapperTrainArgs A{};
-  A.P = *P; A.c = c; A.bits = bits; A.work = work; A.n = n; A.nwg = (n + TR_TPB - 1) / TR_TPB;
-  A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
-  A.round_bits = round_bits; A.update_stats = update_stats;
-  A.gstat = gathered; A.gworld = stage >= 2 ? world : 0;
-  const dim3 g(A.nwg), t(MTH);
-  switch (stage) {
-    case 1: hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<1>, g, t, 0, stream, A); break;
-    case 2: hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<2>, g, t, 0, stream, A); break;
-    case 3: hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<3>, g, t, 0, stream, A); break;
-    default: hipLaunchKernelGGL(mcaq_mapper_fwd_kernel<4>, g, t, 0, stream, A); break;
-  }
-  return (int)hipGetLastError();
+  const mcaq_mapper_seg g{c, bits, work, nullptr, nullptr, nullptr, n};
+  return mcaq_mapper_train_forward_stage_multi(P, &g, 1, min_bits, max_bits, temperature, momentum, round_bits,
+                                               update_stats, stage, &gathered, world, stream);
 }
 
 int mcaq_mapper_train_backward_stage(const mcaq_mapper_params* P, const float* c, int n, const float* gbits,
                                      float min_bits, float max_bits, float temperature, float* work, float* gc,
                                      float* gpart, int stage, const float* gsums, const float* gathered1, int world,
                                      hipStream_t stream) {
-  using namespace mcaq;
-  if (!P || !c || !gbits || !gc || !gpart || !work || n < 1 || stage < 1 || stage > 4 || world < 1 ||
-      (stage <= 3 && (!gsums || !gathered1)))
-    return (int)hipErrorInvalidValue;
-  MapperTrainArgs A{};
-  A.P = *P; A.c = c; A.gbits = gbits; A.gc = gc; A.work = work; A.gpart = gpart; A.n = n;
-  A.nwg = (n + TR_TPB - 1) / TR_TPB;
-  A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature;
-  A.gbsum = gsums; A.gstat1 = gathered1; A.gworld = stage <= 3 ? world : 0;
-  const dim3 g(A.nwg), t(MTH);
-  switch (stage) {
-    case 4: hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<4>, g, t, 0, stream, A); break;
-    case 3: hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<3>, g, t, 0, stream, A); break;
-    case 2: hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<2>, g, t, 0, stream, A); break;
-    default: hipLaunchKernelGGL(mcaq_mapper_bwd_kernel<1>, g, t, 0, stream, A); break;
-  }
-  return (int)hipGetLastError();
+  const mcaq_mapper_seg g{c, nullptr, work, gbits, gc, gpart, n};
+  return mcaq_mapper_train_backward_stage_multi(P, &g, 1, min_bits, max_bits, temperature, stage, &gsums, &gathered1,
+                                                world, stream);
 }
 
 int mcaq_mapper_train_reduce(const float* work, int n, int kind, int layer, float* out, hipStream_t stream) {
@@ -2561,11 +2668,8 @@ int mcaq_mapper_train_reduce(const float* work, int n, int kind, int layer, floa
 
 int mcaq_mapper_train_grad_reduce(int n, const float* gpart, float* gparams, int accumulate, hipStream_t stream) {
   using namespace mcaq;
-  if (!gpart || !gparams || n < 1) return (int)hipErrorInvalidValue;
-  const int nwg = (n + TR_TPB - 1) / TR_TPB;
-  hipLaunchKernelGGL(mcaq_tr_reduce_kernel, dim3((MG_SIZE + 255) / 256), dim3(256), 0, stream, gpart, nwg,
-                     (int)MG_SIZE, (int)MG_SIZE, gparams, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
+  if (n < 1) return (int)hipErrorInvalidValue;
+  return reduce_one(gpart, (n + TR_TPB - 1) / TR_TPB, MG_SIZE, gparams, accumulate, stream);
 }
 
 size_t mcaq_mapper_gpart_floats(int n) { return (size_t)((n + mcaq::TR_TPB - 1) / mcaq::TR_TPB) * mcaq::MG_SIZE; }
@@ -2576,56 +2680,21 @@ int mcaq_head_train_backward(const mcaq_cmlp_params* P, const float* phi, const 
                              int ht, int wt, float* gcraw, float* gparams, float* gpart, int accumulate,
                              hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !phi || !craw || !gC || !gcraw || !gpart || B < 1 || ht < 1 || wt < 1)
-    return (int)hipErrorInvalidValue;
-  HeadTrainArgs A{};
-  A.P = *P; A.phi = phi; A.craw = craw; A.gC = gC; A.gcraw = gcraw; A.gpart = gpart;
-  A.B = B; A.ht = ht; A.wt = wt; A.n = B * ht * wt; A.nwg = (A.n + TR_TPB - 1) / TR_TPB;
-  const size_t lb = (size_t)53 * ht * wt * sizeof(float);
-  if (lb > 160 * 1024 - 1024) return (int)hipErrorInvalidValue;
-  const size_t lc = (size_t)(TR_TPB * CB_ST + CB_NW * TR_TPB + 4096) * sizeof(float);
-  static int set = 0;
-  if (!set) {
-    hipError_t e = hipFuncSetAttribute((const void*)mcaq_cmlp_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lc);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mcaq_bilateral_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 1;
-  }
-  hipLaunchKernelGGL(mcaq_bilateral_bwd_kernel, dim3(B), dim3(BL_TH), lb, stream, A);
-  hipLaunchKernelGGL(mcaq_cmlp_bwd_kernel, dim3(A.nwg), dim3(64 * CB_NW), lc, stream, A);
-  if (gparams)   // NULL: the caller reduces gpart (mcaq_head_train_grad_reduce)
-    hipLaunchKernelGGL(mcaq_tr_reduce_kernel, dim3((CG_SIZE + 255) / 256), dim3(256), 0, stream, (const float*)gpart,
-                       A.nwg, (int)CG_SIZE, (int)CG_SIZE, gparams, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
+  const mcaq_head_seg g{phi, craw, gC, gcraw, gpart, B, ht, wt};
+  const int e = mcaq_head_train_backward_multi_ride(P, &g, 1, nullptr, 0, stream);
+  if (e || !gparams) return e;   // gparams NULL: the caller reduces gpart (mcaq_head_train_grad_reduce)
+  return reduce_one(gpart, (B * ht * wt + TR_TPB - 1) / TR_TPB, CG_SIZE, gparams, accumulate, stream);
 }
 
 int mcaq_mapper_train_forward_multi(const mcaq_mapper_params* P, const mcaq_mapper_seg* segs, int nseg,
                                     float min_bits, float max_bits, float temperature, float momentum,
                                     int round_bits, int update_stats, hipStream_t stream) {
   using namespace mcaq;
-  // one launch per stage for every segment: several segments updating the
-  // shared running statistics in-kernel would race (update_stats 1)
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || (nseg > 1 && update_stats == 1)) return (int)hipErrorInvalidValue;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.bits || !g.work || g.n < 1) return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.bits = g.bits; A.work = g.work; A.n = g.n; A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
-    A.round_bits = round_bits; A.update_stats = update_stats; A.wg0 = wg;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
-  const dim3 g(wg), t(MTH);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<1>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<2>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<3>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<4>, g, t, 0, stream, M);
+  const int wg = mapper_segs(M, false, P, segs, nseg, min_bits, max_bits, temperature, momentum, round_bits,
+                             update_stats);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  for (int st = 1; st <= 4; ++st) launch_mapper_fwd_stage(st, wg, stream, M);
   return (int)hipGetLastError();
 }
 
@@ -2634,29 +2703,12 @@ int mcaq_mapper_train_forward_stage_multi(const mcaq_mapper_params* P, const mca
                                           int round_bits, int update_stats, int stage, const float* const* gathered,
                                           int world, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || (nseg > 1 && update_stats == 1) || stage < 1 || stage > 4 ||
-      world < 1 || (stage >= 2 && !gathered))
-    return (int)hipErrorInvalidValue;
+  if (stage < 1 || stage > 4 || world < 1 || (stage >= 2 && !gathered)) return (int)hipErrorInvalidValue;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.bits || !g.work || g.n < 1 || (stage >= 2 && !gathered[k])) return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.bits = g.bits; A.work = g.work; A.n = g.n; A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
-    A.round_bits = round_bits; A.update_stats = update_stats; A.wg0 = wg;
-    A.gstat = stage >= 2 ? gathered[k] : nullptr; A.gworld = stage >= 2 ? world : 0;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
-  const dim3 g(wg), t(MTH);
-  switch (stage) {
-    case 1: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<1>, g, t, 0, stream, M); break;
-    case 2: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<2>, g, t, 0, stream, M); break;
-    case 3: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<3>, g, t, 0, stream, M); break;
-    default: hipLaunchKernelGGL(mcaq_mapper_fwd_multi_kernel<4>, g, t, 0, stream, M); break;
-  }
+  const int wg = mapper_segs(M, false, P, segs, nseg, min_bits, max_bits, temperature, momentum, round_bits,
+                             update_stats, stage >= 2 ? world : 0, gathered);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  launch_mapper_fwd_stage(stage, wg, stream, M);
   return (int)hipGetLastError();
 }
 
@@ -2665,31 +2717,12 @@ int mcaq_mapper_train_backward_stage_multi(const mcaq_mapper_params* P, const mc
                                            const float* const* gsums, const float* const* gathered1, int world,
                                            hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || stage < 1 || stage > 4 || world < 1 ||
-      (stage <= 3 && (!gsums || !gathered1)))
-    return (int)hipErrorInvalidValue;
+  if (stage < 1 || stage > 4 || world < 1 || (stage <= 3 && (!gsums || !gathered1))) return (int)hipErrorInvalidValue;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.gbits || !g.gc || !g.gpart || !g.work || g.n < 1 || (stage <= 3 && (!gsums[k] || !gathered1[k])))
-      return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.gbits = g.gbits; A.gc = g.gc; A.work = g.work; A.gpart = g.gpart; A.n = g.n;
-    A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.wg0 = wg;
-    A.gbsum = stage <= 3 ? gsums[k] : nullptr; A.gstat1 = stage <= 3 ? gathered1[k] : nullptr;
-    A.gworld = stage <= 3 ? world : 0;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
-  const dim3 g(wg), t(MTH);
-  switch (stage) {
-    case 4: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<4>, g, t, 0, stream, M); break;
-    case 3: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<3>, g, t, 0, stream, M); break;
-    case 2: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<2>, g, t, 0, stream, M); break;
-    default: hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<1>, g, t, 0, stream, M); break;
-  }
+  const int wg = mapper_segs(M, true, P, segs, nseg, min_bits, max_bits, temperature, 0.0f, 0, 0,
+                             stage <= 3 ? world : 0, nullptr, gsums, gathered1);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  launch_mapper_bwd_stage(stage, wg, stream, M);
   return (int)hipGetLastError();
 }
 
@@ -2697,37 +2730,16 @@ int mcaq_mapper_train_backward_multi_ride(const mcaq_mapper_params* P, const mca
                                           float min_bits, float max_bits, float temperature,
                                           const mcaq_reduce_seg* rsegs, int nr, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || nr < 0 || nr > TR_MAXSEG || (nr > 0 && !rsegs))
-    return (int)hipErrorInvalidValue;
   TrMulti<TrReduceSeg> R{};
-  for (int k = 0; k < nr; ++k) {
-    const mcaq_reduce_seg& g = rsegs[k];
-    if (!g.part || !g.out || g.nparts < 1 || g.stride < g.count || g.count < 1 || g.count != rsegs[0].count)
-      return (int)hipErrorInvalidValue;
-    R.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
-  }
-  R.nseg = nr;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.gbits || !g.gc || !g.gpart || !g.work || g.n < 1) return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.gbits = g.gbits; A.gc = g.gc; A.work = g.work; A.gpart = g.gpart; A.n = g.n;
-    A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.wg0 = wg;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
-  const dim3 g(wg), t(MTH);
+  const int wg = mapper_segs(M, true, P, segs, nseg, min_bits, max_bits, temperature);
+  if (wg < 0 || !reduce_segs(R, rsegs, nr, false, true)) return (int)hipErrorInvalidValue;
   if (nr > 0)
-    hipLaunchKernelGGL(mcaq_mapper_bwd_ride_kernel<4>, dim3(wg + (nr * R.s[0].count + MTH - 1) / MTH), t, 0, stream,
-                       M, R, wg);
+    hipLaunchKernelGGL(mcaq_mapper_bwd_ride_kernel<4>, dim3(wg + (nr * R.s[0].count + MTH - 1) / MTH), dim3(MTH), 0,
+                       stream, M, R, wg);
   else
-    hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<4>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<3>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<2>, g, t, 0, stream, M);
-  hipLaunchKernelGGL(mcaq_mapper_bwd_multi_kernel<1>, g, t, 0, stream, M);
+    launch_mapper_bwd_stage(4, wg, stream, M);
+  for (int st = 3; st >= 1; --st) launch_mapper_bwd_stage(st, wg, stream, M);
   return (int)hipGetLastError();
 }
 
@@ -2778,19 +2790,10 @@ int mcaq_mapper_train_forward_fused(const mcaq_mapper_params* P, const mcaq_mapp
                                     int round_bits, int update_stats, void* sync, size_t sync_bytes,
                                     hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || (nseg > 1 && update_stats == 1)) return (int)hipErrorInvalidValue;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.bits || !g.work || g.n < 1) return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.bits = g.bits; A.work = g.work; A.n = g.n; A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.momentum = momentum;
-    A.round_bits = round_bits; A.update_stats = update_stats; A.wg0 = wg;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
+  const int wg = mapper_segs(M, false, P, segs, nseg, min_bits, max_bits, temperature, momentum, round_bits,
+                             update_stats);
+  if (wg < 0) return (int)hipErrorInvalidValue;
   const int le = mapx_layout(M, wg, sync, sync_bytes);
   if (le) return le;
   hipLaunchKernelGGL(mcaq_mapper_fwd_fused_kernel, dim3(wg), dim3(MTH), 0, stream, M);
@@ -2802,28 +2805,10 @@ int mcaq_mapper_train_backward_fused(const mcaq_mapper_params* P, const mcaq_map
                                      const mcaq_reduce_seg* rsegs, int nr, void* sync, size_t sync_bytes,
                                      hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || nr < 0 || nr > TR_MAXSEG || (nr > 0 && !rsegs))
-    return (int)hipErrorInvalidValue;
   TrMulti<TrReduceSeg> R{};
-  for (int k = 0; k < nr; ++k) {
-    const mcaq_reduce_seg& g = rsegs[k];
-    if (!g.part || !g.out || g.nparts < 1 || g.stride < g.count || g.count < 1 || g.count != rsegs[0].count)
-      return (int)hipErrorInvalidValue;
-    R.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
-  }
-  R.nseg = nr;
   TrMulti<MapperTrainArgs> M{};
-  int wg = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_mapper_seg& g = segs[k];
-    if (!g.c || !g.gbits || !g.gc || !g.gpart || !g.work || g.n < 1) return (int)hipErrorInvalidValue;
-    MapperTrainArgs& A = M.s[k];
-    A.P = *P; A.c = g.c; A.gbits = g.gbits; A.gc = g.gc; A.work = g.work; A.gpart = g.gpart; A.n = g.n;
-    A.nwg = (g.n + TR_TPB - 1) / TR_TPB;
-    A.min_bits = min_bits; A.max_bits = max_bits; A.temperature = temperature; A.wg0 = wg;
-    wg += A.nwg;
-  }
-  M.nseg = nseg;
+  const int wg = mapper_segs(M, true, P, segs, nseg, min_bits, max_bits, temperature);
+  if (wg < 0 || !reduce_segs(R, rsegs, nr, false, true)) return (int)hipErrorInvalidValue;
   const int le = mapx_layout(M, wg, sync, sync_bytes);
   if (le) return le;
   const int rwg = nr > 0 ? (nr * R.s[0].count + MTH - 1) / MTH : 0;
@@ -2834,58 +2819,13 @@ int mcaq_mapper_train_backward_fused(const mcaq_mapper_params* P, const mcaq_map
 int mcaq_head_train_backward_multi_ride(const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg,
                                         const mcaq_reduce_seg* rsegs, int nr, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || nr < 0 || nr > TR_MAXSEG || (nr > 0 && !rsegs))
-    return (int)hipErrorInvalidValue;
   TrMulti<TrReduceSeg> R{};
-  for (int k = 0; k < nr; ++k) {
-    const mcaq_reduce_seg& g = rsegs[k];
-    if (!g.part || (!g.out && k == 0) || g.nparts < 1 || g.stride < g.count || g.count < 1 || g.count != rsegs[0].count)
-      return (int)hipErrorInvalidValue;
-    R.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
-  }
-  R.nseg = nr;
-  TrMulti<HeadTrainArgs> Mb{}, Mc{};
-  int wb = 0, wc = 0;
-  size_t lb = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_head_seg& g = segs[k];
-    if (!g.phi || !g.craw || !g.gC || !g.gcraw || !g.gpart || g.B < 1 || g.ht < 1 || g.wt < 1)
-      return (int)hipErrorInvalidValue;
-    HeadTrainArgs A{};
-    A.P = *P; A.phi = g.phi; A.craw = g.craw; A.gC = g.gC; A.gcraw = g.gcraw; A.gpart = g.gpart;
-    A.B = g.B; A.ht = g.ht; A.wt = g.wt; A.n = g.B * g.ht * g.wt; A.nwg = (A.n + TR_TPB - 1) / TR_TPB;
-    const size_t l = (size_t)53 * g.ht * g.wt * sizeof(float);
-    if (l > 160 * 1024 - 1024) return (int)hipErrorInvalidValue;
-    lb = l > lb ? l : lb;
-    Mb.s[k] = A; Mb.s[k].wg0 = wb; wb += A.B;      // bilateral: one workgroup per image
-    Mc.s[k] = A; Mc.s[k].wg0 = wc; wc += A.nwg;    // MLP: 64 tiles per workgroup
-  }
-  Mb.nseg = Mc.nseg = nseg;
-  const size_t lc = (size_t)(TR_TPB * CB_ST + CB_NW * TR_TPB + 4096) * sizeof(float);
-  static int set = 0;
-  if (!set) {
-    hipError_t e = hipFuncSetAttribute((const void*)mcaq_cmlp_bwd_multi_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lc);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mcaq_bilateral_bwd_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 1;
-  }
-  if (nr > 0) {
-    static int set_r = 0;
-    if (!set_r) {
-      const hipError_t e = hipFuncSetAttribute((const void*)mcaq_bilateral_bwd_ride_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-      if (e != hipSuccess) return (int)e;
-      set_r = 1;
-    }
-    const int rw = (R.s[0].count + BL_TH - 1) / BL_TH;
-    hipLaunchKernelGGL(mcaq_bilateral_bwd_ride_kernel, dim3(wb + rw), dim3(BL_TH), lb, stream, Mb, R, wb);
-  } else {
-    hipLaunchKernelGGL(mcaq_bilateral_bwd_multi_kernel, dim3(wb), dim3(BL_TH), lb, stream, Mb);
-  }
-  hipLaunchKernelGGL(mcaq_cmlp_bwd_multi_kernel, dim3(wc), dim3(64 * CB_NW), lc, stream, Mc);
+  HeadLaunch H{};
+  if (!head_segs(H, P, segs, nseg) || !reduce_segs(R, rsegs, nr, true, true)) return (int)hipErrorInvalidValue;
+  int e = tr_lds_attr((const void*)mcaq_cmlp_bwd_multi_kernel, (int)CMLP_LDS);
+  if (!e) e = launch_bilateral_bwd(H, R, stream);
+  if (e) return e;
+  hipLaunchKernelGGL(mcaq_cmlp_bwd_multi_kernel, dim3(H.wc), dim3(64 * CB_NW), CMLP_LDS, stream, H.Mc);
   return (int)hipGetLastError();
 }
 
@@ -2902,89 +2842,29 @@ int mcaq_head_train_backward_fused(const mcaq_cmlp_params* P, const mcaq_head_se
                                    const mcaq_reduce_seg* rsegs, int nr, float* out, int accumulate, float scale,
                                    void* sync, size_t sync_bytes, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !segs || nseg < 1 || nseg > TR_MAXSEG || nr < 0 || nr > TR_MAXSEG || (nr > 0 && !rsegs) || !out ||
-      !sync || ((uintptr_t)sync & 7) != 0)
-    return (int)hipErrorInvalidValue;
   TrMulti<TrReduceSeg> R{};
-  for (int k = 0; k < nr; ++k) {
-    const mcaq_reduce_seg& g = rsegs[k];
-    if (!g.part || (!g.out && k == 0) || g.nparts < 1 || g.stride < g.count || g.count < 1 || g.count != rsegs[0].count)
-      return (int)hipErrorInvalidValue;
-    R.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
-  }
-  R.nseg = nr;
-  TrMulti<HeadTrainArgs> Mb{}, Mc{};
-  int wb = 0, wc = 0;
-  size_t lb = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_head_seg& g = segs[k];
-    if (!g.phi || !g.craw || !g.gC || !g.gcraw || !g.gpart || g.B < 1 || g.ht < 1 || g.wt < 1)
-      return (int)hipErrorInvalidValue;
-    HeadTrainArgs A{};
-    A.P = *P; A.phi = g.phi; A.craw = g.craw; A.gC = g.gC; A.gcraw = g.gcraw; A.gpart = g.gpart;
-    A.B = g.B; A.ht = g.ht; A.wt = g.wt; A.n = g.B * g.ht * g.wt; A.nwg = (A.n + TR_TPB - 1) / TR_TPB;
-    const size_t l = (size_t)53 * g.ht * g.wt * sizeof(float);
-    if (l > 160 * 1024 - 1024) return (int)hipErrorInvalidValue;
-    lb = l > lb ? l : lb;
-    Mb.s[k] = A; Mb.s[k].wg0 = wb; wb += A.B;
-    Mc.s[k] = A; Mc.s[k].wg0 = wc; wc += A.nwg;
-  }
-  Mb.nseg = Mc.nseg = nseg;
-  if (wc > MAPPER_COOP_MAX_WG || sync_bytes < mcaq_head_sync_bytes(wc)) return (int)hipErrorInvalidValue;
-  const size_t lc = (size_t)(TR_TPB * CB_ST + CB_NW * TR_TPB + 4096) * sizeof(float);
+  HeadLaunch H{};
+  if (!out || !sync || ((uintptr_t)sync & 7) != 0 || !head_segs(H, P, segs, nseg) ||
+      !reduce_segs(R, rsegs, nr, true, true))
+    return (int)hipErrorInvalidValue;
+  if (H.wc > MAPPER_COOP_MAX_WG || sync_bytes < mcaq_head_sync_bytes(H.wc)) return (int)hipErrorInvalidValue;
   static_assert((size_t)TR_TPB * CB_ST >= (size_t)CG_SIZE + MAPPER_COOP_MAX_WG, "slice buffer in the tile vectors");
-  static int set = 0;
-  if (!set) {
-    hipError_t e = hipFuncSetAttribute((const void*)mcaq_cmlp_bwd_fused_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lc);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mcaq_bilateral_bwd_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)mcaq_bilateral_bwd_ride_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 1;
-  }
-  if (nr > 0) {
-    const int rw = (R.s[0].count + BL_TH - 1) / BL_TH;
-    hipLaunchKernelGGL(mcaq_bilateral_bwd_ride_kernel, dim3(wb + rw), dim3(BL_TH), lb, stream, Mb, R, wb);
-  } else {
-    hipLaunchKernelGGL(mcaq_bilateral_bwd_multi_kernel, dim3(wb), dim3(BL_TH), lb, stream, Mb);
-  }
-  const CmlpRed cr{static_cast<unsigned*>(sync), out, accumulate, scale, wc};
-  hipLaunchKernelGGL(mcaq_cmlp_bwd_fused_kernel, dim3(wc), dim3(64 * CB_NW), lc, stream, Mc, cr);
+  int e = tr_lds_attr((const void*)mcaq_cmlp_bwd_fused_kernel, (int)CMLP_LDS);
+  if (!e) e = launch_bilateral_bwd(H, R, stream);
+  if (e) return e;
+  const CmlpRed cr{static_cast<unsigned*>(sync), out, accumulate, scale, H.wc};
+  hipLaunchKernelGGL(mcaq_cmlp_bwd_fused_kernel, dim3(H.wc), dim3(64 * CB_NW), CMLP_LDS, stream, H.Mc, cr);
   return (int)hipGetLastError();
 }
 
 int mcaq_smask_train_backward_multi(const mcaq_smask_seg* segs, int nseg, hipStream_t stream) {
   using namespace mcaq;
-  if (!segs || nseg < 1 || nseg > TR_MAXSEG) return (int)hipErrorInvalidValue;
   TrMulti<MaskTrainArgs> M{};
-  int wg = 0;
-  size_t lb = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_smask_seg& g = segs[k];
-    if (!g.bits || !g.absmean || !g.gm || !g.gbits || !g.gpart || g.B < 1 || g.ht < 1 || g.wt < 1 || g.H < g.ht ||
-        g.W < g.wt)
-      return (int)hipErrorInvalidValue;
-    MaskTrainArgs& A = M.s[k];
-    A.P = g.P; A.bits = g.bits; A.absmean = g.absmean; A.gm = g.gm; A.gbits = g.gbits; A.gpart = g.gpart;
-    A.B = g.B; A.H = g.H; A.W = g.W; A.ht = g.ht; A.wt = g.wt; A.accumulate = g.accumulate; A.wg0 = wg;
-    A.stage = smask_stage_ok(g.absmean, g.gm, g.H, g.W, g.ht, g.wt) ? 1 : 0;
-    wg += g.B;
-    const size_t l = smask_lds_bytes(g.H, g.W, g.ht, g.wt, A.stage != 0);
-    if (l > 160 * 1024 - 1024) return (int)hipErrorInvalidValue;
-    lb = l > lb ? l : lb;
-  }
-  M.nseg = nseg;
-  static int set = 0;
-  if (!set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)mcaq_smask_bwd_multi_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 1;
-  }
+  size_t lb;
+  const int wg = smask_segs(M, segs, nseg, lb);
+  if (wg < 0) return (int)hipErrorInvalidValue;
+  const int e = tr_lds_attr((const void*)mcaq_smask_bwd_multi_kernel, TR_LDS_MAX);
+  if (e) return e;
   hipLaunchKernelGGL(mcaq_smask_bwd_multi_kernel, dim3(wg), dim3(SM_TH), lb, stream, M);
   return (int)hipGetLastError();
 }
@@ -3022,13 +2902,8 @@ static int qat_smask_backward_losses(const mcaq_qat_smask_seg* segs, int nseg, c
     lb = l > lb ? l : lb;
   }
   M.nseg = nseg;
-  static int set = 0;
-  if (!set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)mcaq_smask_bwd_multi_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 1;
-  }
+  const int ae = tr_lds_attr((const void*)mcaq_smask_bwd_multi_kernel, TR_LDS_MAX);
+  if (ae) return ae;
   hipLaunchKernelGGL(mcaq_smask_bwd_multi_kernel, dim3(wg), dim3(SM_TH), lb, stream, M);
   return (int)hipGetLastError();
 }
@@ -3074,18 +2949,10 @@ int mcaq_tile_losses_forward(const float* const* bits, const int* dims, int nseg
 
 int mcaq_train_reduce_multi(const mcaq_reduce_seg* segs, int nseg, int chain, hipStream_t stream) {
   using namespace mcaq;
-  if (!segs || nseg < 1 || nseg > TR_MAXSEG) return (int)hipErrorInvalidValue;
   TrMulti<TrReduceSeg> M{};
+  if (nseg < 1 || !reduce_segs(M, segs, nseg, chain != 0, chain != 0)) return (int)hipErrorInvalidValue;
   int cmax = 0;
-  for (int k = 0; k < nseg; ++k) {
-    const mcaq_reduce_seg& g = segs[k];
-    if (!g.part || (!g.out && !(chain && k > 0)) || g.nparts < 1 || g.stride < g.count || g.count < 1)
-      return (int)hipErrorInvalidValue;
-    if (chain && g.count != segs[0].count) return (int)hipErrorInvalidValue;
-    M.s[k] = TrReduceSeg{g.part, g.out, g.nparts, g.stride, g.count, g.accumulate, g.scale};
-    cmax = g.count > cmax ? g.count : cmax;
-  }
-  M.nseg = nseg;
+  for (int k = 0; k < nseg; ++k) cmax = M.s[k].count > cmax ? M.s[k].count : cmax;
   hipLaunchKernelGGL(mcaq_tr_reduce_multi_kernel, dim3((cmax + 255) / 256, chain ? 1 : nseg), dim3(256), 0, stream, M,
                      chain ? 1 : 0);
   return (int)hipGetLastError();
@@ -3093,11 +2960,8 @@ int mcaq_train_reduce_multi(const mcaq_reduce_seg* segs, int nseg, int chain, hi
 
 int mcaq_head_train_grad_reduce(int n, const float* gpart, float* gparams, int accumulate, hipStream_t stream) {
   using namespace mcaq;
-  if (!gpart || !gparams || n < 1) return (int)hipErrorInvalidValue;
-  const int nwg = (n + TR_TPB - 1) / TR_TPB;
-  hipLaunchKernelGGL(mcaq_tr_reduce_kernel, dim3((CG_SIZE + 255) / 256), dim3(256), 0, stream, gpart, nwg,
-                     (int)CG_SIZE, (int)CG_SIZE, gparams, accumulate ? 1 : 0);
-  return (int)hipGetLastError();
+  if (n < 1) return (int)hipErrorInvalidValue;
+  return reduce_one(gpart, (n + TR_TPB - 1) / TR_TPB, CG_SIZE, gparams, accumulate, stream);
 }
 
 size_t mcaq_smask_gpart_floats(int B) { return (size_t)B * mcaq::SG_SIZE; }
@@ -3151,25 +3015,10 @@ int mcaq_smask_train_backward(const mcaq_smask_params* P, const float* bits, con
                               int B, int H, int W, int ht, int wt, float* gbits, int accumulate, float* gparams,
                               float* gpart, hipStream_t stream) {
   using namespace mcaq;
-  if (!P || !bits || !absmean || !gm || !gbits || !gparams || !gpart || B < 1 || ht < 1 || wt < 1 || H < ht || W < wt)
-    return (int)hipErrorInvalidValue;
-  MaskTrainArgs A{};
-  A.P = *P; A.bits = bits; A.absmean = absmean; A.gm = gm; A.gbits = gbits; A.gpart = gpart;
-  A.B = B; A.H = H; A.W = W; A.ht = ht; A.wt = wt; A.accumulate = accumulate;
-  A.stage = smask_stage_ok(absmean, gm, H, W, ht, wt) ? 1 : 0;
-  const size_t lb = smask_lds_bytes(H, W, ht, wt, A.stage != 0);
-  if (lb > 160 * 1024 - 1024) return (int)hipErrorInvalidValue;   // m(p) gradient of one image staged in LDS
-  static int set = 0;
-  if ((int)lb > set) {
-    const hipError_t e = hipFuncSetAttribute((const void*)mcaq_smask_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024 - 1024);
-    if (e != hipSuccess) return (int)e;
-    set = 160 * 1024 - 1024;
-  }
-  hipLaunchKernelGGL(mcaq_smask_bwd_kernel, dim3(B), dim3(SM_TH), lb, stream, A);
-  hipLaunchKernelGGL(mcaq_tr_reduce_kernel, dim3(1), dim3(256), 0, stream, (const float*)gpart, B, (int)SG_SIZE,
-                     (int)SG_SIZE, gparams, 0);
-  return (int)hipGetLastError();
+  if (!P || !gparams) return (int)hipErrorInvalidValue;
+  const mcaq_smask_seg g{*P, bits, absmean, gm, gbits, gpart, B, H, W, ht, wt, accumulate};
+  const int e = mcaq_smask_train_backward_multi(&g, 1, stream);
+  return e ? e : reduce_one(gpart, B, SG_SIZE, gparams, 0, stream);
 }
 
 }  // extern "C"

@@ -302,7 +302,7 @@ class _HeadMulti(torch.autograd.Function):
         params = ctx.saved_tensors[2 * n:]
         L = abi.lib()
         dev = craws[0].device
-        q = abi.CmlpParams(*[_p(p.detach()) for p in params])
+        q = core._ptr_struct(abi.CmlpParams, params)
         segs = (abi.HeadSeg * n)()
         gparts, keep = [], []
         for i in range(n):
@@ -540,15 +540,7 @@ class _MapperMulti(torch.autograd.Function):
         L = abi.lib()
         dev = cs[0].device
         bns = [net[i] for i in (1, 4, 7)]
-        q = abi.MapperParams()
-        for k, t in zip(("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4"),
-                        (net[0].weight, net[0].bias, net[3].weight, net[3].bias, net[6].weight, net[6].bias,
-                         net[9].weight, net[9].bias)):
-            setattr(q, k, _p(t.detach()))
-        for i, bn in enumerate(bns, 1):
-            for k, t in (("g", bn.weight), ("be", bn.bias), ("rm", bn.running_mean), ("rv", bn.running_var),
-                         ("nbt", bn.num_batches_tracked)):
-                setattr(q, "%s%d" % (k, i), _p(t.detach()) if t is not None else None)
+        q = core._mapper_params(net)
         T = max(float(temperature), 0.1) if temperature is not None else 0.0
         segs = (abi.MapperSeg * n)()
         cfs, works, bits = [], [], []
@@ -743,7 +735,7 @@ class _SoftMaskMulti(torch.autograd.Function):
             keep += [b, gm, gp]
             gbs.append(gb); gflats.append(gf)
             s = segs[i]
-            s.P = abi.SmaskParams(*[_p(p.detach()) for p in ctx.mods[i].net.parameters()])
+            s.P = core._ptr_struct(abi.SmaskParams, ctx.mods[i].net.parameters())
             s.bits, s.absmean, s.gm, s.gbits, s.gpart = _p(b), _p(absmeans[i]), _p(gm), _p(gb), _p(gp)
             s.B, s.H, s.W, s.ht, s.wt, s.accumulate = B, H, W, ht, wt, 0
             r = rsegs[i]
@@ -913,7 +905,7 @@ class _MaskQuantMulti(torch.autograd.Function):
             gbs.append(gb)
             gflats.append(gf)
             sg = segs[i]
-            sg.P = abi.SmaskParams(*[_p(p.detach()) for p in ctx.mods[i].net.parameters()])
+            sg.P = core._ptr_struct(abi.SmaskParams, ctx.mods[i].net.parameters())
             sg.bits, sg.absmean, sg.qat_work, sg.gbits, sg.gpart = _p(bits[i]), _p(absmeans[i]), _p(work), _p(gb), \
                 _p(gp)
             sg.B, sg.C, sg.H, sg.W, sg.ht, sg.wt = B, C, H, W, ht, wt
