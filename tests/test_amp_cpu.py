@@ -59,13 +59,13 @@ def test_cpu_path_result_type_vs_reference(key):
 
 
 def _qmaxnt():
-    src = open(os.path.join(ROOT, "mcaq_yolo_amd", "csrc", "mcaq_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "mcaq_yolo_amd", "csrc", "mcaq_quant.h")).read()
     return int(re.search(r"constexpr int QMAXNT = (\d+);", src).group(1))
 
 
 def _tile_ok(H, W, ht, wt, nbits, qmaxnt):
-    """mcaq_quant's tile-aligned path (csrc/mcaq_kernels.hip, `vec` geometry +
-    `tile_ok`), restated: the only pass-2 kernel that reads a half map."""
+    """mcaq_quant's tile-aligned family (csrc/mcaq_quant.h, quant_plan: `vec` geometry +
+    `tile`), restated: the only pass-2 kernels that read a half map."""
     sh = sw = 0
     while (ht << sh) < H:
         sh += 1
