@@ -55,10 +55,11 @@ def _step(fused, B=4, seed=5, mapper="mlp", temperature=1.0, shapes=((64, 80), (
         h = _hooks(mapper)
         gen = torch.Generator(device="cpu").manual_seed(seed)
         feats = []
-        for c, s in shapes:
-            lo = torch.randn(B, c, s // 8, s // 8, generator=gen)
-            hi = torch.randn(B, c, s, s, generator=gen)
-            up = torch.nn.functional.interpolate(lo, size=(s, s), mode="bilinear", align_corners=False)
+        for c, s in shapes:                  # s: the side of a square map, or (H, W)
+            sh, sw = (s, s) if isinstance(s, int) else s
+            lo = torch.randn(B, c, max(sh // 8, 1), max(sw // 8, 1), generator=gen)
+            hi = torch.randn(B, c, sh, sw, generator=gen)
+            up = torch.nn.functional.interpolate(lo, size=(sh, sw), mode="bilinear", align_corners=False)
             feats.append(torch.nn.functional.silu(1.5 * hi + 2 * up).to(DEV).requires_grad_(True))
         outs, aux = h.forward_features(feats, temperature=temperature)
         gens = [torch.randn(o.shape, generator=gen).to(DEV) * 1e-3 for o in outs]
@@ -116,9 +117,10 @@ def test_fused_train_step_config5_bs16_matches_torch_path():
     _check_step_vs_torch(1.0, B=16)
 
 
-def _check_step_vs_torch(temperature, B=4):
-    o1, a1, gx1, g1, b1 = _step(True, B=B, temperature=temperature)
-    o0, a0, gx0, g0, b0 = _step(False, B=B, temperature=temperature)
+def _check_step_vs_torch(temperature, B=4, shapes=None):
+    kw = {} if shapes is None else {"shapes": shapes}
+    o1, a1, gx1, g1, b1 = _step(True, B=B, temperature=temperature, **kw)
+    o0, a0, gx0, g0, b0 = _step(False, B=B, temperature=temperature, **kw)
     for a, b in zip(a1, a0):
         assert torch.equal(a["complexity"], b["complexity"]), "analyzer forward (morph kernel) differs"
         _rel(a["bit_map"], b["bit_map"], 1e-5)
@@ -162,7 +164,11 @@ def test_fused_mapper_vs_reference_fixture():
 
 def test_fused_softmask_backward_vs_autograd():
     """LearnedSoftMask backward: the fused kernel vs torch autograd of the
-    tile-sized restatement (quantization.py:213-239), ragged grids included."""
+    tile-sized restatement (quantization.py:213-239), at four shapes whose
+    maps are whole multiples of their tile grids, with H * W a multiple of 4
+    and 16-byte-aligned planes (the staged branch only).  The ragged,
+    unstaged and unaligned shapes are compared with a float64 reference in
+    test_train_values_gpu.py."""
     from mcaq_yolo_amd import core
     W = load_weights()
     gen = torch.Generator(device="cpu").manual_seed(9)
