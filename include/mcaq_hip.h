@@ -44,7 +44,7 @@ typedef void* hipEvent_t;
 extern "C" {
 #endif
 
-#define MCAQ_ABI_VERSION 30
+#define MCAQ_ABI_VERSION 31
 /* feature-map element types (mcaq_stats_scale.dtype, mcaq_quant_scale.dtype,
  * mcaq_qat_scale.dtype) */
 #define MCAQ_DTYPE_F32 0
@@ -367,13 +367,16 @@ typedef struct {
 size_t mcaq_mapper_work_floats(int n);
 int mcaq_mapper_train_forward(const mcaq_mapper_params* P, const float* c, int n, float min_bits, float max_bits,
                               float temperature, float momentum, int round_bits, int update_stats, float* bits,
-                              float* work, unsigned* grid_sync, hipStream_t stream);
+                              float* work, hipStream_t stream);
 /* gc (n), gparams (4609: mapping_network parameters() order); 5 launches */
 size_t mcaq_mapper_gpart_floats(int n);
 int mcaq_mapper_train_backward(const mcaq_mapper_params* P, const float* c, int n, const float* gbits,
                                float min_bits, float max_bits, float temperature, float* work, float* gc,
-                               float* gparams, float* gpart, int accumulate, unsigned* grid_sync,
-                               hipStream_t stream);
+                               float* gparams, float* gpart, int accumulate, hipStream_t stream);
+/* The two calls above run one launch per batch-statistics barrier; the
+ * one-launch form is mcaq_mapper_train_forward_fused / _backward_fused below
+ * (the statistics exchanged as granules inside the launch, at most
+ * mcaq_mapper_fused_max_wg() * 64 tiles). */
 /* Batch sharded over `world` ranks with process-group BatchNorm (the train-
  * mode mapper of a DDP QAT step, dist.GroupBatchNorm1d semantics): the same
  * kernels one stage per call, the caller's collectives between them.
@@ -419,10 +422,6 @@ int mcaq_ema_stats_multi_running(const mcaq_ema_seg* segs, int nseg, const mcaq_
 int mcaq_morph_ema(const mcaq_morph_scale* scales, int nscales, const mcaq_ema_seg* esegs, int ne,
                    const mcaq_mapper_params* P, const float* const* works, const int* ns, int count, float momentum,
                    hipStream_t stream);
-/* grid_sync: NULL (one launch per batch-statistics barrier), or 2 zeroed
- * uint32 that launches on one stream share (each launch leaves them zeroed):
- * forward and backward then run as ONE launch each, with grid-wide barriers
- * between the stages (n <= 256 * 64 tiles). */
 /* analyzer head: gC (B, ht, wt) -> gcraw (B, ht, wt) work, gparams (2881:
  * complexity_mlp parameters() order); phi (B*ht*wt, 8), craw = the MLP output
  * before the bilateral; 3 launches (2 with gparams NULL: the caller then
@@ -578,19 +577,6 @@ int mcaq_train_reduce_multi(const mcaq_reduce_seg* segs, int nseg, int chain, hi
  * launch of their own (nr = 0: none). */
 int mcaq_head_train_backward_multi_ride(const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg,
                                         const mcaq_reduce_seg* rsegs, int nr, hipStream_t stream);
-/* mcaq_head_train_backward_multi_ride with the complexity MLP's parameter
- * reduction inside its launch (round 6): out (+)= the chain sum of every
- * segment's partials, last segment first (as mcaq_train_reduce_multi with
- * chain 1 over the segments' gpart, accumulate / scale as there), through
- * `sync` (mcaq_head_sync_bytes(total MLP workgroups = sum of ceil(B ht wt /
- * 64)), zeroed before first use and whenever the layout changes, one launch
- * at a time; word 1 nonzero after a timed-out exchange).  Bit-identical to
- * the separate reduction; gpart is not written.  hipErrorInvalidValue above
- * mcaq_mapper_fused_max_wg() workgroups. */
-size_t mcaq_head_sync_bytes(int total_wg);
-int mcaq_head_train_backward_fused(const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg,
-                                   const mcaq_reduce_seg* rsegs, int nr, float* out, int accumulate, float scale,
-                                   void* sync, size_t sync_bytes, hipStream_t stream);
 /* mcaq_mapper_train_backward_multi with per-segment reductions (as
  * mcaq_train_reduce_multi with chain 0, segments of equal count) riding on
  * its first (output-layer) stage launch as extra workgroups - the soft masks'
@@ -622,8 +608,8 @@ int mcaq_mapper_train_backward_fused(const mcaq_mapper_params* P, const mcaq_map
                                      hipStream_t stream);
 
 /* gparams of the mapper / head backward: accumulate != 0 adds to gparams
- * (the parameters' persistent gradient storage), 0 overwrites it; NULL
- * (without grid_sync): no reduction launch - the partials stay in gpart for
+ * (the parameters' persistent gradient storage), 0 overwrites it; NULL:
+ * no reduction launch - the partials stay in gpart for
  * the matching *_grad_reduce call, which a caller with several streams
  * orders itself. */
 

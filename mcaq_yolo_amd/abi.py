@@ -9,7 +9,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libmcaq_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2   # MCAQ_DTYPE_*
 ARITH_FP32, ARITH_REFERENCE = 0, 1            # MCAQ_ARITH_* (mcaq_quant_scale.arith)
 MAX_SEGMENTS = 9   # MCAQ_MAX_SEGMENTS: segments (hook scale x batch) per launch
@@ -169,8 +169,7 @@ EXPORTS = ("mcaq_abi_version", "mcaq_launch_spatial_quantization", "mcaq_stats",
            "mcaq_mapper_train_forward_multi", "mcaq_mapper_train_backward_multi", "mcaq_head_train_backward_multi",
            "mcaq_smask_train_backward_multi", "mcaq_train_reduce_multi", "mcaq_ema_stats_multi",
            "mcaq_mapper_train_forward_stage_multi", "mcaq_mapper_train_backward_stage_multi", "mcaq_clip_adamw", "mcaq_clip_adamw_work_floats",
-           "mcaq_clip_adamw_sync_bytes", "mcaq_clip_adamw_fused", "mcaq_head_sync_bytes",
-           "mcaq_head_train_backward_fused",
+           "mcaq_clip_adamw_sync_bytes", "mcaq_clip_adamw_fused",
            "mcaq_bit_budget_forward", "mcaq_qat_smask_backward_multi", "mcaq_qat_forward_budget",
            "mcaq_ema_stats_multi_running", "mcaq_head_train_backward_multi_ride",
            "mcaq_stats_pack", "mcaq_morph_ema", "mcaq_mapper_train_backward_multi_ride", "mcaq_dp_unpack",
@@ -225,9 +224,9 @@ def _declare(lib):
         getattr(lib, n).restype = SZ
         getattr(lib, n).argtypes = [I]
     lib.mcaq_mapper_train_forward.restype = I
-    lib.mcaq_mapper_train_forward.argtypes = [ctypes.POINTER(MapperParams), P, I, Fl, Fl, Fl, Fl, I, I, P, P, P, P]
+    lib.mcaq_mapper_train_forward.argtypes = [ctypes.POINTER(MapperParams), P, I, Fl, Fl, Fl, Fl, I, I, P, P, P]
     lib.mcaq_mapper_train_backward.restype = I
-    lib.mcaq_mapper_train_backward.argtypes = [ctypes.POINTER(MapperParams), P, I, P, Fl, Fl, Fl, P, P, P, P, I, P, P]
+    lib.mcaq_mapper_train_backward.argtypes = [ctypes.POINTER(MapperParams), P, I, P, Fl, Fl, Fl, P, P, P, P, I, P]
     lib.mcaq_mapper_train_forward_stage.restype = I
     lib.mcaq_mapper_train_forward_stage.argtypes = [ctypes.POINTER(MapperParams), P, I, Fl, Fl, Fl, Fl, I, I, P, P, I, P,
                                                     I, P]
@@ -269,11 +268,6 @@ def _declare(lib):
     lib.mcaq_mapper_train_backward_fused.restype = I
     lib.mcaq_mapper_train_backward_fused.argtypes = [ctypes.POINTER(MapperParams), ctypes.POINTER(MapperSeg), I, Fl,
                                                      Fl, Fl, ctypes.POINTER(ReduceSeg), I, P, SZ, P]
-    lib.mcaq_head_sync_bytes.restype = SZ
-    lib.mcaq_head_sync_bytes.argtypes = [I]
-    lib.mcaq_head_train_backward_fused.restype = I
-    lib.mcaq_head_train_backward_fused.argtypes = [ctypes.POINTER(CmlpParams), ctypes.POINTER(HeadSeg), I,
-                                                   ctypes.POINTER(ReduceSeg), I, P, I, Fl, P, SZ, P]
     lib.mcaq_head_train_backward_multi_ride.restype = I
     lib.mcaq_head_train_backward_multi_ride.argtypes = [ctypes.POINTER(CmlpParams), ctypes.POINTER(HeadSeg), I,
                                                         ctypes.POINTER(ReduceSeg), I, P]

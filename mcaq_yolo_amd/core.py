@@ -1256,36 +1256,12 @@ class concurrent_scales:
         self.events[key] = ev
 
 
-# one-launch train-mode mapper (grid barriers between its batch-statistics
-# stages) instead of one launch per stage: measured slower at config 5 (the
-# agent-scope release / acquire around each barrier costs more than a kernel
-# boundary: forward 46.7 vs 37.6 us, backward 68.7 vs ~55 us per scale,
-# profiles/r03_qat/one_launch_mapper_ab.txt), so off by default
-MAPPER_ONE_LAUNCH = False
-_GRID_SYNC = {}
-
-
-def _grid_sync_counter(device):
-    """Zeroed uint32 pair for the mapper's grid barriers: one persistent buffer
-    per (device, stream) - launches on one stream run one after another and
-    each leaves it zeroed; launches on different streams get different
-    buffers.  Created inside a graph capture, the buffer's zero fill is
-    captured too (every replay re-zeroes it).  None when MAPPER_ONE_LAUNCH is
-    off (multi-launch path)."""
-    if not MAPPER_ONE_LAUNCH:
-        return None
-    key = (torch.device(device), torch.cuda.current_stream(device).cuda_stream)
-    buf = _GRID_SYNC.get(key)
-    if buf is None:
-        buf = torch.zeros(2, dtype=torch.int32, device=device)
-        _GRID_SYNC[key] = buf
-    return buf
-
-
 class _MapperTrainFn(torch.autograd.Function):
     """ComplexityToBitMappingNetwork in train mode (batch-statistics
     BatchNorm, running stats updated, straight-through clamp / round) on the
-    fused kernels: 4 forward launches, 5 backward launches."""
+    fused kernels: 4 forward launches (one per batch-statistics barrier), 4 + 1
+    backward launches (the last the parameter reduction).  The one-launch form
+    is the multi-scale step's (train_step.MAPPER_FUSED)."""
 
     @staticmethod
     def forward(ctx, mod, c, temperature, return_continuous, *params):
@@ -1308,7 +1284,7 @@ class _MapperTrainFn(torch.autograd.Function):
             abi.check(L.mcaq_mapper_train_forward(ctypes.byref(q), _p(cf), n, mod.min_bits, mod.max_bits, T,
                                                   float(bns[0].momentum), 0 if return_continuous else 1,
                                                   2 if conc is not None else 1, _p(bits),
-                                                  _p(work), _p(_grid_sync_counter(c.device)), _stream()),
+                                                  _p(work), _stream()),
                       "mcaq_mapper_train_forward")
             if conc is not None:
                 conc.defer_mapper(mod, q, work, n, float(bns[0].momentum))
@@ -1353,14 +1329,14 @@ class _MapperTrainFn(torch.autograd.Function):
             # the scales' reductions into the shared flat buffer, one after another
             abi.check(L.mcaq_mapper_train_backward(ctypes.byref(ctx.q), _p(cf), n, _p(gb), mod.min_bits,
                                                    mod.max_bits, ctx.T, _p(work), _p(gc), None, _p(gpart), acc,
-                                                   None, _stream()), "mcaq_mapper_train_backward")
+                                                   _stream()), "mcaq_mapper_train_backward")
             conc.ordered(mod._gsink, lambda: abi.check(
                 L.mcaq_mapper_train_grad_reduce(n, _p(gpart), _p(gflat), acc, _stream()),
                 "mcaq_mapper_train_grad_reduce"))
         elif ctx.pg is None:
             abi.check(L.mcaq_mapper_train_backward(ctypes.byref(ctx.q), _p(cf), n, _p(gb), mod.min_bits,
                                                    mod.max_bits, ctx.T, _p(work), _p(gc), _p(gflat), _p(gpart), acc,
-                                                   _p(_grid_sync_counter(cf.device)), _stream()),
+                                                   _stream()),
                       "mcaq_mapper_train_backward")
         else:
             # BN backward sums (S1, S2) of each layer all-reduced over the

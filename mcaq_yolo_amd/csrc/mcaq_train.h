@@ -208,7 +208,7 @@ __device__ __forceinline__ void map_bn(const mcaq_mapper_params& P, int L, const
 }
 
 constexpr int MW = 8;               // waves per mapper workgroup (lane = tile, waves split the features)
-constexpr int MAPPER_COOP_MAX_WG = 256;   // one-launch mapper (grid barrier / granule exchanges) up to this many workgroups
+constexpr int MAPX_MAX_WG = 256;    // fused (one-launch, granule-exchange) mapper up to this many workgroups
 constexpr int MTH = 64 * MW;
 
 // ---- fused mapper launches: the batch-statistic partials exchanged inside
@@ -222,7 +222,7 @@ constexpr int MTH = 64 * MW;
 // epoch word is read by every wave at launch and advanced by the segment's
 // first workgroup after its last exchange (every workgroup of the segment has
 // read it by then), so granules of earlier launches never match.  A buffer
-// serves one segment layout and starts zeroed (train_step._sync_buffer).
+// serves one segment layout and starts zeroed (train_step._mapx_buffer).
 // Bounded spins: a timeout sets the status word and goes on (tests check it).
 #ifndef MCAQ_MAPX_SLEEP   // s_sleep between two sweeps of unpublished granules
 #define MCAQ_MAPX_SLEEP 2
@@ -676,51 +676,6 @@ __device__ __forceinline__ void mapper_fwd_stage(const MapperTrainArgs& A, MapFw
   }
 }
 
-// grid-wide barrier of a launch whose workgroups are all resident (the mapper
-// grids are n / 64 <= a few hundred 512-thread workgroups): every wave
-// releases its writes at agent scope, one thread counts in and waits, every
-// wave acquires.  `bar` is a persistent zeroed counter the launch leaves
-// zeroed (mapper_grid_exit); a bounded spin never hangs the GPU.
-__device__ __forceinline__ void mapper_grid_sync(unsigned* bar, unsigned target) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0;
-    while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target && spins < (1u << 24)) {
-      __builtin_amdgcn_s_sleep(1);
-      ++spins;
-    }
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-// the last workgroup out resets the counters for the next launch on the stream
-__device__ __forceinline__ void mapper_grid_exit(unsigned* bar, int nwg) {
-  if (threadIdx.x == 0) {
-    const unsigned out = __hip_atomic_fetch_add(bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (out == (unsigned)nwg - 1) {
-      __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(bar + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// the four forward stages in one launch, grid barriers between them
-__global__ __launch_bounds__(MTH) void mcaq_mapper_fwd_coop_kernel(MapperTrainArgs A, unsigned* bar) {
-  __shared__ MapFwdLds L;
-  const unsigned n = (unsigned)A.nwg;
-  mapper_fwd_stage<1>(A, L);
-  mapper_grid_sync(bar, n);
-  mapper_fwd_stage<2>(A, L);
-  mapper_grid_sync(bar, 2 * n);
-  mapper_fwd_stage<3>(A, L);
-  mapper_grid_sync(bar, 3 * n);
-  mapper_fwd_stage<4>(A, L);
-  mapper_grid_exit(bar, A.nwg);
-}
-
 // backward stage S (4, 3, 2, 1): gradient of layer S's output activation ->
 // (BN S-1 backward inputs, weight partials of layer S)
 //   S = 4: g_bits -> g_a4 -> g_h3 -> g_y3 (through ReLU), partials of W4 / b4
@@ -1110,29 +1065,6 @@ __global__ __launch_bounds__(64) void mcaq_mapper_reduce_kernel(const float* wor
   }
 }
 
-// the four backward stages and the parameter reduction in one launch
-__global__ __launch_bounds__(MTH) void mcaq_mapper_bwd_coop_kernel(MapperTrainArgs A, unsigned* bar, float* gparams,
-                                                                   int accumulate) {
-  __shared__ MapBwdLds L;
-  const unsigned n = (unsigned)A.nwg;
-  mapper_bwd_stage<4>(A, L);
-  mapper_grid_sync(bar, n);
-  mapper_bwd_stage<3>(A, L);
-  mapper_grid_sync(bar, 2 * n);
-  mapper_bwd_stage<2>(A, L);
-  mapper_grid_sync(bar, 3 * n);
-  mapper_bwd_stage<1>(A, L);
-  mapper_grid_sync(bar, 4 * n);
-  // parameter gradients: sum of the workgroups' partials in workgroup order,
-  // each workgroup a slice of the flat vector
-  for (int e = (int)blockIdx.x * MTH + (int)threadIdx.x; e < MG_SIZE; e += (int)n * MTH) {
-    float sum = 0.0f;
-    for (int w = 0; w < A.nwg; ++w) sum += A.gpart[(size_t)w * MG_SIZE + e];
-    gparams[e] = accumulate ? gparams[e] + sum : sum;
-  }
-  mapper_grid_exit(bar, A.nwg);
-}
-
 // ============================================================================
 // analyzer head backward: clamp + bilateral adjoint (per image), complexity
 // MLP backward (per tile)
@@ -1260,10 +1192,7 @@ constexpr int CB_ST = 8 + 64 * 4 + 32 * 4 + 1 + 4;   // per-tile LDS vector (flo
 enum : int { CB_PHI = 0, CB_R1 = 8, CB_GA1 = 72, CB_GY1 = 136, CB_GYX1 = 200, CB_R2 = 264, CB_GA2 = 296,
              CB_GY2 = 328, CB_GYX2 = 360, CB_GA3 = 392 };
 
-// kX (fused launch, mcaq_cmlp_bwd_fused_kernel): the weight partials
-// published as granules of gx (this workgroup's CG_SIZE slots) with `tag`
-template <bool kX = false>
-__device__ __forceinline__ void mcaq_cmlp_bwd_body(const HeadTrainArgs& A, mapx_t* gx = nullptr, unsigned tag = 0) {
+__device__ __forceinline__ void mcaq_cmlp_bwd_body(const HeadTrainArgs& A) {
   constexpr int NW = CB_NW, F1 = 64 / NW, F2 = 32 / NW, NTH = 64 * NW;
   extern __shared__ float smem_tr[];
   float* sv = smem_tr;                       // [TR_TPB][CB_ST]
@@ -1413,10 +1342,7 @@ __device__ __forceinline__ void mcaq_cmlp_bwd_body(const HeadTrainArgs& A, mapx_
   // ---- weight partials over the workgroup's tiles (invalid lanes carry zero
   // gradients).  W2 (32 x 64): thread = one row x 4 columns.
   float* gp = A.gpart + (size_t)wgi * CG_SIZE;
-  auto put = [&](int e, float x) {
-    if constexpr (kX) mapx_put(gx + e, tag, x);
-    else gp[e] = x;
-  };
+  auto put = [&](int e, float x) { gp[e] = x; };
   auto tvec = [&](int u) { return sv + u * CB_ST; };
   {
     // one 16 x 16 block of W2 per wave on v_mfma_f32_16x16x4_f32: a
@@ -2079,73 +2005,6 @@ __global__ __launch_bounds__(MTH) void mcaq_mapper_bwd_multi_kernel(TrMulti<Mapp
 __global__ __launch_bounds__(BL_TH) void mcaq_bilateral_bwd_multi_kernel(TrMulti<HeadTrainArgs> M) {
   mcaq_bilateral_bwd_body(tr_seg(M));
 }
-// the complexity MLP's backward of every segment with its parameter
-// reduction in the same launch: every workgroup publishes its CG_SIZE weight
-// partials as granules (mapx_*: write-through, the epoch tag in each), then
-// sums a slice of the elements over every workgroup's partials - the chain
-// of mcaq_tr_reduce_multi (segments last scale first, each in workgroup
-// order, accumulate / scale as tr_chain_elem), so the values are identical.
-// Sync buffer (mcaq_head_sync_bytes): word 0 the epoch, word 1 the status,
-// granules from byte 256, [workgroup][CG_SIZE].  Every workgroup must be
-// resident at once (at most MAPPER_COOP_MAX_WG).
-struct CmlpRed {
-  unsigned* sync;
-  float* out;
-  int accumulate;
-  float scale;
-  int nwg;             // workgroups of the launch (every segment's)
-};
-__global__ __launch_bounds__(64 * CB_NW) void mcaq_cmlp_bwd_fused_kernel(TrMulti<HeadTrainArgs> M, CmlpRed R) {
-  extern __shared__ float smem_tr[];
-  const HeadTrainArgs& A = tr_seg(M);
-  mapx_t* const gran = reinterpret_cast<mapx_t*>(R.sync + MAPX_HDR);
-  const unsigned tag = __builtin_amdgcn_readfirstlane(
-                           __hip_atomic_load(R.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
-  mcaq_cmlp_bwd_body<true>(A, gran + (size_t)blockIdx.x * CG_SIZE, tag);
-  __syncthreads();
-  // this workgroup's slice of the elements, every workgroup's partial of each
-  // into LDS (one granule load per thread per pass, all in flight), then one
-  // thread per element sums them in the chain's order
-  const int W = R.nwg, per = (CG_SIZE + W - 1) / W;
-  const int e0 = (int)blockIdx.x * per, ne = imin_(per, CG_SIZE - e0);
-  float* buf = smem_tr;                       // [ne][W]
-  const int tid = (int)threadIdx.x;
-  constexpr int NTH = 64 * CB_NW;
-  for (int i0 = 0; i0 < ne * W; i0 += 4 * NTH) {
-    mapx_t* gp[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = imin_(i0 + r * NTH + tid, ne * W - 1);
-      const int el = i / W, w = i - el * W;
-      gp[r] = gran + (size_t)w * CG_SIZE + e0 + el;
-    }
-    float v[4];
-    if (ne > 0) mapx_get<4>(gp, tag, v, R.sync + 1);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = i0 + r * NTH + tid;
-      if (i < ne * W) buf[i] = v[r];
-    }
-  }
-  __syncthreads();
-  if (blockIdx.x == 0 && tid == 0)   // every workgroup published (slice 0 read them all): next epoch
-    __hip_atomic_fetch_add(R.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (int el = tid; el < ne; el += NTH) {   // a slice can exceed the workgroup (few workgroups)
-    const int e = e0 + el;
-    const float* row = buf + (size_t)el * W;
-    const bool sc = R.scale != 0.0f && R.scale != 1.0f;
-    float acc = 0.0f;
-    for (int c = 0; c < M.nseg; ++c) {
-      const HeadTrainArgs& G = M.s[M.nseg - 1 - c];   // the chain: last segment first
-      float sum = 0.0f;
-      for (int w = 0; w < G.nwg; ++w) sum = sum + row[G.wg0 + w];
-      acc = c == 0 ? ((R.accumulate && !sc) ? R.out[e] + sum : sum) : acc + sum;
-    }
-    if (sc) acc = R.accumulate ? R.out[e] + acc * R.scale : acc * R.scale;
-    R.out[e] = acc;
-  }
-}
-
 __global__ __launch_bounds__(64 * CB_NW) void mcaq_cmlp_bwd_multi_kernel(TrMulti<HeadTrainArgs> M) {
   mcaq_cmlp_bwd_body(tr_seg(M));
 }
@@ -2270,7 +2129,7 @@ __global__ __launch_bounds__(MTH) void mcaq_mapper_bwd_ride_kernel(TrMulti<Mappe
 // statistics exchanged as granules between them (mapx_*; the arithmetic and
 // its order are the staged launches', so the results are bit-identical).
 // Every workgroup must be resident at once: the launcher admits at most
-// MAPPER_COOP_MAX_WG workgroups (one 512-thread workgroup per CU is enough).
+// MAPX_MAX_WG workgroups (one 512-thread workgroup per CU is enough).
 __global__ __launch_bounds__(MTH) void mcaq_mapper_fwd_fused_kernel(TrMulti<MapperTrainArgs> M) {
   __shared__ MapFwdLds L;
   __shared__ float s_a[TR_TPB][65];
@@ -2516,35 +2375,24 @@ size_t mcaq_mapper_work_floats(int n) { return mcaq::mapper_work_floats(n); }
 
 int mcaq_mapper_train_forward(const mcaq_mapper_params* P, const float* c, int n, float min_bits, float max_bits,
                               float temperature, float momentum, int round_bits, int update_stats, float* bits,
-                              float* work, unsigned* grid_sync, hipStream_t stream) {
+                              float* work, hipStream_t stream) {
   using namespace mcaq;
   const mcaq_mapper_seg g{c, bits, work, nullptr, nullptr, nullptr, n};
   TrMulti<MapperTrainArgs> M{};
   const int wg = mapper_segs(M, false, P, &g, 1, min_bits, max_bits, temperature, momentum, round_bits, update_stats);
   if (wg < 0) return (int)hipErrorInvalidValue;
-  if (grid_sync && wg <= MAPPER_COOP_MAX_WG) {
-    hipLaunchKernelGGL(mcaq_mapper_fwd_coop_kernel, dim3(wg), dim3(MTH), 0, stream, M.s[0], grid_sync);
-    return (int)hipGetLastError();
-  }
   for (int st = 1; st <= 4; ++st) launch_mapper_fwd_stage(st, wg, stream, M);
   return (int)hipGetLastError();
 }
 
 int mcaq_mapper_train_backward(const mcaq_mapper_params* P, const float* c, int n, const float* gbits,
                                float min_bits, float max_bits, float temperature, float* work, float* gc,
-                               float* gparams, float* gpart, int accumulate, unsigned* grid_sync,
-                               hipStream_t stream) {
+                               float* gparams, float* gpart, int accumulate, hipStream_t stream) {
   using namespace mcaq;
-  if (!gparams && grid_sync) return (int)hipErrorInvalidValue;
   const mcaq_mapper_seg g{c, nullptr, work, gbits, gc, gpart, n};
   TrMulti<MapperTrainArgs> M{};
   const int wg = mapper_segs(M, true, P, &g, 1, min_bits, max_bits, temperature);
   if (wg < 0) return (int)hipErrorInvalidValue;
-  if (grid_sync && wg <= MAPPER_COOP_MAX_WG) {
-    hipLaunchKernelGGL(mcaq_mapper_bwd_coop_kernel, dim3(wg), dim3(MTH), 0, stream, M.s[0], grid_sync, gparams,
-                       accumulate ? 1 : 0);
-    return (int)hipGetLastError();
-  }
   for (int st = 4; st >= 1; --st) launch_mapper_bwd_stage(st, wg, stream, M);
   if (!gparams) return (int)hipGetLastError();   // the caller reduces gpart (mcaq_mapper_train_grad_reduce)
   return reduce_one(gpart, wg, MG_SIZE, gparams, accumulate, stream);
@@ -2759,7 +2607,7 @@ size_t mcaq_mapper_sync_bytes(int total_wg) {
   return total_wg < 1 ? 0 : (size_t)MAPX_HDR * 4 + (size_t)3 * MAPX_STRIDE * 8 * total_wg;
 }
 
-int mcaq_mapper_fused_max_wg(void) { return mcaq::MAPPER_COOP_MAX_WG; }
+int mcaq_mapper_fused_max_wg(void) { return mcaq::MAPX_MAX_WG; }
 
 }  // extern "C"
 
@@ -2768,7 +2616,7 @@ namespace mcaq {
 // the total workgroup count): header words, then per segment 3 exchange
 // regions of nwg x MAPX_STRIDE granules, segments in order
 static int mapx_layout(TrMulti<MapperTrainArgs>& M, int wg, void* sync, size_t sync_bytes) {
-  if (!sync || wg > MAPPER_COOP_MAX_WG || sync_bytes < mcaq_mapper_sync_bytes(wg) ||
+  if (!sync || wg > MAPX_MAX_WG || sync_bytes < mcaq_mapper_sync_bytes(wg) ||
       ((uintptr_t)sync & 7) != 0)
     return (int)hipErrorInvalidValue;
   unsigned* hdr = static_cast<unsigned*>(sync);
@@ -2831,30 +2679,6 @@ int mcaq_head_train_backward_multi_ride(const mcaq_cmlp_params* P, const mcaq_he
 
 int mcaq_head_train_backward_multi(const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg, hipStream_t stream) {
   return mcaq_head_train_backward_multi_ride(P, segs, nseg, nullptr, 0, stream);
-}
-
-size_t mcaq_head_sync_bytes(int total_wg) {
-  using namespace mcaq;
-  return total_wg < 1 ? 0 : (size_t)MAPX_HDR * 4 + (size_t)total_wg * CG_SIZE * 8;
-}
-
-int mcaq_head_train_backward_fused(const mcaq_cmlp_params* P, const mcaq_head_seg* segs, int nseg,
-                                   const mcaq_reduce_seg* rsegs, int nr, float* out, int accumulate, float scale,
-                                   void* sync, size_t sync_bytes, hipStream_t stream) {
-  using namespace mcaq;
-  TrMulti<TrReduceSeg> R{};
-  HeadLaunch H{};
-  if (!out || !sync || ((uintptr_t)sync & 7) != 0 || !head_segs(H, P, segs, nseg) ||
-      !reduce_segs(R, rsegs, nr, true, true))
-    return (int)hipErrorInvalidValue;
-  if (H.wc > MAPPER_COOP_MAX_WG || sync_bytes < mcaq_head_sync_bytes(H.wc)) return (int)hipErrorInvalidValue;
-  static_assert((size_t)TR_TPB * CB_ST >= (size_t)CG_SIZE + MAPPER_COOP_MAX_WG, "slice buffer in the tile vectors");
-  int e = tr_lds_attr((const void*)mcaq_cmlp_bwd_fused_kernel, (int)CMLP_LDS);
-  if (!e) e = launch_bilateral_bwd(H, R, stream);
-  if (e) return e;
-  const CmlpRed cr{static_cast<unsigned*>(sync), out, accumulate, scale, H.wc};
-  hipLaunchKernelGGL(mcaq_cmlp_bwd_fused_kernel, dim3(H.wc), dim3(64 * CB_NW), CMLP_LDS, stream, H.Mc, cr);
-  return (int)hipGetLastError();
 }
 
 int mcaq_smask_train_backward_multi(const mcaq_smask_seg* segs, int nseg, hipStream_t stream) {

@@ -21,6 +21,7 @@ per-tensor quantizers keep their per-scale pieces in between.
 """
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -33,6 +34,19 @@ def _cmlp_params(an):
 
 
 _SM_BLOBS = {"key": None, "blobs": None, "primed": False}
+
+
+def _sm_key(ps):
+    """The soft-mask blob cache's key: the parameters themselves (weakly held)
+    with their storage and versions.  Addresses and versions alone also match
+    another module's parameters allocated where a freed module's were, whose
+    blobs would then be the freed module's weights."""
+    return tuple((weakref.ref(p), p.data_ptr(), p._version) for p in ps)
+
+
+def _sm_hit(key, ps):
+    return key is not None and len(key) == len(ps) and \
+        all(r() is p and a == p.data_ptr() and v == p._version for (r, a, v), p in zip(key, ps))
 _PREPACK = {"pending": None}
 
 
@@ -65,8 +79,7 @@ def _prepack(an, mods):
         return
     capturing = torch.cuda.is_current_stream_capturing()
     ckey = tuple((t.data_ptr(), t._version, t.device) for t in cps)
-    skey = tuple((p.data_ptr(), p._version) for p in sps)
-    if not capturing and (ckey == an._blob.key or skey == _SM_BLOBS["key"]):
+    if not capturing and (ckey == an._blob.key or _sm_hit(_SM_BLOBS["key"], sps)):
         return
     segs, o = core._pack_segs(parts, mfma)
     if o > core._CM_BLOB:
@@ -82,7 +95,7 @@ def _prepack(an, mods):
     _PREPACK["pending"] = (core._pack_array(segs), len(segs), out, segs)
     an._blob.prime(out[:core._CM_BLOB], None if capturing else ckey)
     _SM_BLOBS["blobs"] = [out[core._CM_BLOB + i * stride:core._CM_BLOB + (i + 1) * stride] for i in range(len(mods))]
-    _SM_BLOBS["key"] = None if capturing else skey
+    _SM_BLOBS["key"] = None if capturing else _sm_key(sps)
     _SM_BLOBS["primed"] = True
 
 
@@ -94,15 +107,14 @@ def _softmask_blobs(mods):
     ps = [p for m in mods for p in m.net.parameters()]
     if _SM_BLOBS["primed"]:
         _SM_BLOBS["primed"] = False
-        if _SM_BLOBS["key"] is None or _SM_BLOBS["key"] == tuple((p.data_ptr(), p._version) for p in ps):
+        if _SM_BLOBS["key"] is None or _sm_hit(_SM_BLOBS["key"], ps):
             return _SM_BLOBS["blobs"]
     if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in ps) or \
             len(ps) > abi.MCAQ_PACK_MAXSEG or any(sum(p.numel() for p in m.net.parameters()) != core._SM_SIZE
                                                   for m in mods):
         return [m.blob() for m in mods]
-    key = tuple((p.data_ptr(), p._version) for p in ps)
     capturing = torch.cuda.is_current_stream_capturing()
-    if capturing or key != _SM_BLOBS["key"]:
+    if capturing or not _sm_hit(_SM_BLOBS["key"], ps):
         stride = (core._SM_SIZE + 3) // 4 * 4
         segs = (abi.PackSeg * len(ps))()
         k = 0
@@ -115,7 +127,7 @@ def _softmask_blobs(mods):
         out = torch.empty(len(mods) * stride, device=ps[0].device)
         abi.check(abi.lib().mcaq_pack(segs, len(ps), _p(out), out.numel(), _stream()), "mcaq_pack")
         _SM_BLOBS["blobs"] = [out[i * stride:(i + 1) * stride] for i in range(len(mods))]
-        _SM_BLOBS["key"] = None if capturing else key
+        _SM_BLOBS["key"] = None if capturing else _sm_key(ps)
     return _SM_BLOBS["blobs"]
 
 
@@ -321,22 +333,13 @@ class _HeadMulti(torch.autograd.Function):
         mod_params = _cmlp_params(ctx.an)
         sink = ctx.an._gsink.target(mod_params) if len(mod_params) == len(params) else None
         gflat, acc = sink if sink is not None else (torch.empty(core._CM_SIZE, device=dev), 0)
-        sync = _sync_buffer(ctx.an, dev, [c.numel() for c in craws], L.mcaq_head_sync_bytes) if HEAD_FUSED else None
-        if sync is not None:
-            # the MLP's parameter reduction inside its own launch; the mapper's
-            # (if pending) riding on the bilateral launch
-            abi.check(L.mcaq_head_train_backward_fused(ctypes.byref(q), segs, n, ride[0] if ride else None,
-                                                       ride[1] if ride else 0, _p(gflat), acc, 0.0, _p(sync),
-                                                       sync.numel() * 8, _stream()),
-                      "mcaq_head_train_backward_fused")
+        if ride is not None:     # the mapper's gradient reduction as extra workgroups of the bilateral launch
+            abi.check(L.mcaq_head_train_backward_multi_ride(ctypes.byref(q), segs, n, ride[0], ride[1],
+                                                            _stream()), "mcaq_head_train_backward_multi_ride")
         else:
-            if ride is not None:     # the mapper's gradient reduction as extra workgroups of the bilateral launch
-                abi.check(L.mcaq_head_train_backward_multi_ride(ctypes.byref(q), segs, n, ride[0], ride[1],
-                                                                _stream()), "mcaq_head_train_backward_multi_ride")
-            else:
-                abi.check(L.mcaq_head_train_backward_multi(ctypes.byref(q), segs, n, _stream()),
-                          "mcaq_head_train_backward_multi")
-            _reduce_chain(gparts, gflat, acc, core._CM_SIZE)
+            abi.check(L.mcaq_head_train_backward_multi(ctypes.byref(q), segs, n, _stream()),
+                      "mcaq_head_train_backward_multi")
+        _reduce_chain(gparts, gflat, acc, core._CM_SIZE)
         grads = (None,) * len(params) if sink is not None else tuple(core._split_flat(gflat, params))
         return (None, None, None) + (None,) * n + grads
 
@@ -417,48 +420,32 @@ DP_GLOBAL_MAPPER = True
 MAPPER_FUSED = os.environ.get("MCAQ_MAPPER_FUSED", "1") != "0"
 
 
-def _sync_buffer(mod, dev, ns, nbytes):
-    """An in-launch exchange's sync buffer for segments of ns tiles (64 per
-    workgroup): one per module and segment layout, zeroed when made (epochs
-    and granules start over); None above the resident-workgroup limit."""
+def _mapx_buffer(mod, dev, ns):
+    """The fused mapper launches' sync buffer (forward and backward share it)
+    for segments of ns tiles (64 per workgroup): one per module and segment
+    layout, zeroed when made (epochs and granules start over); None above the
+    resident-workgroup limit."""
     L = abi.lib()
     wgs = tuple((int(n) + 63) // 64 for n in ns)
     total = sum(wgs)
     if total > L.mcaq_mapper_fused_max_wg():
         return None
     cache = mod.__dict__.setdefault("_mapx", {})
-    key = (str(dev), nbytes.__name__, wgs)
+    key = (str(dev), wgs)
     buf = cache.get(key)
     if buf is None:
-        buf = torch.zeros((nbytes(total) + 7) // 8, dtype=torch.int64, device=dev)
+        buf = torch.zeros((L.mcaq_mapper_sync_bytes(total) + 7) // 8, dtype=torch.int64, device=dev)
         cache[key] = buf
     return buf
 
 
-def _mapx_buffer(mod, dev, ns):
-    """The fused mapper launches' sync buffer (forward and backward share it)."""
-    return _sync_buffer(mod, dev, ns, abi.lib().mcaq_mapper_sync_bytes) if MAPPER_FUSED else None
-
-
 def mapper_sync_status(mod):
-    """Nonzero when an in-launch exchange of a fused launch of `mod` (the
-    mapper's, or the analyzer head's backward) timed out (its results are
-    then invalid); 0 otherwise.  Synchronises."""
+    """Nonzero when an in-launch exchange of a fused mapper launch of `mod`
+    timed out (its results are then invalid); 0 otherwise.  Synchronises."""
     st = 0
-    for key, buf in getattr(mod, "_mapx", {}).items():
-        w = abi.MAPPER_SYNC_STATUS_WORD if key[1] == "mcaq_mapper_sync_bytes" else abi.ADAMW_SYNC_STATUS_WORD
-        st |= int(buf.view(torch.int32)[w].item())
+    for buf in getattr(mod, "_mapx", {}).values():
+        st |= int(buf.view(torch.int32)[abi.MAPPER_SYNC_STATUS_WORD].item())
     return st
-
-
-# The complexity MLP's backward with its parameter reduction inside the
-# launch (mcaq_head_train_backward_fused: partials exchanged as granules,
-# bit-identical to the separate chain reduction).  Off by default: measured
-# no faster than the separate launch (19.8 vs 13.9 + 5.7 us, step within
-# noise: profiles/r06_fuse/r06_fuse3) - the 2,881 partials per workgroup
-# cost as much written and swept write-through as the launch boundary they
-# replace.  MCAQ_HEAD_FUSED=1 selects it.
-HEAD_FUSED = os.environ.get("MCAQ_HEAD_FUSED", "0") == "1"
 
 
 def _consecutive(ts):
@@ -555,7 +542,7 @@ class _MapperMulti(torch.autograd.Function):
         mom = float(bns[0].momentum)
         pg = core._mapper_group(net) if dp is None else None
         ctx.pg, ctx.gath1, ctx.world, ctx.dp = pg, None, 1, dp
-        sync = _mapx_buffer(mod, dev, [c.numel() for c in cfs]) if pg is None else None
+        sync = _mapx_buffer(mod, dev, [c.numel() for c in cfs]) if MAPPER_FUSED and pg is None else None
         ctx.sync = sync
         if sync is not None:
             abi.check(L.mcaq_mapper_train_forward_fused(ctypes.byref(q), segs, n, mod.min_bits, mod.max_bits, T, mom,

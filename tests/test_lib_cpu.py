@@ -104,7 +104,6 @@ def test_in_launch_exchange_sizes_and_refusals_without_gpu():
     assert mx == 256
     assert lib.mcaq_mapper_sync_bytes(0) == 0
     assert lib.mcaq_mapper_sync_bytes(57) == 64 * 4 + 3 * 129 * 8 * 57
-    assert lib.mcaq_head_sync_bytes(57) == 64 * 4 + 57 * 2881 * 8
     assert lib.mcaq_clip_adamw_sync_bytes(9000, 40) == 64 * 4 + 9 * 40 * 8
     fake = ctypes.c_void_p(0x1000)      # never dereferenced: every call below is refused first
     q = abi.MapperParams()
@@ -128,9 +127,9 @@ def test_in_launch_exchange_sizes_and_refusals_without_gpu():
 
 
 def test_sync_buffers_one_per_module_and_layout():
-    """train_step._sync_buffer: one zeroed buffer per module, size function and
-    segment layout (a layout seen before gets its buffer back), none above
-    the resident-workgroup limit."""
+    """train_step._mapx_buffer: one zeroed buffer per module and segment
+    layout (a layout seen before gets its buffer back), none above the
+    resident-workgroup limit."""
     if not os.path.exists(abi.LIB_PATH):
         pytest.skip("library not built")
     import torch
@@ -140,12 +139,10 @@ def test_sync_buffers_one_per_module_and_layout():
     class M:
         pass
     m = M()
-    b1 = train_step._sync_buffer(m, torch.device("cpu"), [1600, 1600, 400], lib.mcaq_mapper_sync_bytes)
+    b1 = train_step._mapx_buffer(m, torch.device("cpu"), [1600, 1600, 400])
     assert b1.dtype == torch.int64 and b1.numel() * 8 >= lib.mcaq_mapper_sync_bytes(57) and not bool(b1.any())
-    b2 = train_step._sync_buffer(m, torch.device("cpu"), [800, 800, 200], lib.mcaq_mapper_sync_bytes)
+    b2 = train_step._mapx_buffer(m, torch.device("cpu"), [800, 800, 200])
     assert b2 is not b1
-    assert train_step._sync_buffer(m, torch.device("cpu"), [1600, 1600, 400], lib.mcaq_mapper_sync_bytes) is b1
-    h = train_step._sync_buffer(m, torch.device("cpu"), [1600, 1600, 400], lib.mcaq_head_sync_bytes)
-    assert h is not b1 and h.numel() * 8 >= lib.mcaq_head_sync_bytes(57)
-    assert train_step._sync_buffer(m, torch.device("cpu"), [64 * 257], lib.mcaq_mapper_sync_bytes) is None
-    assert len(m._mapx) == 3
+    assert train_step._mapx_buffer(m, torch.device("cpu"), [1600, 1600, 400]) is b1
+    assert train_step._mapx_buffer(m, torch.device("cpu"), [64 * 257]) is None
+    assert len(m._mapx) == 2

@@ -25,10 +25,11 @@ def test_qat_scale_ends_with_dtype():
 
 
 def test_abi_version_30():
-    assert abi.ABI_VERSION == 30
-    assert re.search(r"^#define MCAQ_ABI_VERSION (\d+)", open(HDR).read(), re.M).group(1) == "30"
+    """Named for the ABI that added the dtype field; pins the current number."""
+    assert abi.ABI_VERSION == 31
+    assert re.search(r"^#define MCAQ_ABI_VERSION (\d+)", open(HDR).read(), re.M).group(1) == "31"
     if os.path.exists(abi.LIB_PATH):
-        assert ctypes.CDLL(abi.LIB_PATH).mcaq_abi_version() == 30
+        assert ctypes.CDLL(abi.LIB_PATH).mcaq_abi_version() == 31
 
 
 def _scale(dtype):

@@ -90,18 +90,16 @@ REDUCE_SEG = [("part", None), ("nparts", 0), ("stride", 169), ("count", 0)]
 # ---- the single-scale entries ----------------------------------------------
 def test_mapper_train_forward_refusals(lib):
     def call(P, c, n, bits, work):
-        return lib.mcaq_mapper_train_forward(P, c, n, 2.0, 8.0, 1.0, 0.1, 1, 1, bits, work, None, None)
+        return lib.mcaq_mapper_train_forward(P, c, n, 2.0, 8.0, 1.0, 0.1, 1, 1, bits, work, None)
     base = dict(P=MP, c=FAKE, n=130, bits=FAKE, work=FAKE)
     _refusals(call, base, _nulls("P", "c", "bits", "work") + [{"n": 0}, {"n": -3}])
 
 
 def test_mapper_train_backward_refusals(lib):
-    def call(P, c, n, gbits, work, gc, gparams, gpart, grid_sync):
-        return lib.mcaq_mapper_train_backward(P, c, n, gbits, 2.0, 8.0, 1.0, work, gc, gparams, gpart, 0, grid_sync,
-                                              None)
-    base = dict(P=MP, c=FAKE, n=130, gbits=FAKE, work=FAKE, gc=FAKE, gparams=FAKE, gpart=FAKE, grid_sync=None)
-    _refusals(call, base, _nulls("P", "c", "gbits", "work", "gc", "gpart") + [
-        {"n": 0}, {"gparams": None, "grid_sync": FAKE}])     # the one-launch form reduces in-kernel: needs gparams
+    def call(P, c, n, gbits, work, gc, gparams, gpart):
+        return lib.mcaq_mapper_train_backward(P, c, n, gbits, 2.0, 8.0, 1.0, work, gc, gparams, gpart, 0, None)
+    base = dict(P=MP, c=FAKE, n=130, gbits=FAKE, work=FAKE, gc=FAKE, gparams=FAKE, gpart=FAKE)
+    _refusals(call, base, _nulls("P", "c", "gbits", "work", "gc", "gpart") + [{"n": 0}])
 
 
 def test_mapper_train_forward_stage_refusals(lib):

@@ -77,7 +77,7 @@ def test_mapper_train_forward_backward_equal_one_segment(hooks, n, update_stats)
     work = [torch.zeros(nw, device=DEV) for _ in range(2)]
     bits = [torch.zeros(n, device=DEV) for _ in range(2)]
     _ok(L.mcaq_mapper_train_forward(ctypes.byref(qs[0]), _p(c), n, MIN_B, MAX_B, TEMP, MOM, 1, update_stats,
-                                    _p(bits[0]), _p(work[0]), None, _stream()), "mcaq_mapper_train_forward")
+                                    _p(bits[0]), _p(work[0]), _stream()), "mcaq_mapper_train_forward")
     _ok(L.mcaq_mapper_train_forward_multi(ctypes.byref(qs[1]), _mseg(c, bits[1], work[1]), 1, MIN_B, MAX_B, TEMP, MOM,
                                           1, update_stats, _stream()), "mcaq_mapper_train_forward_multi")
     assert torch.equal(bits[0], bits[1])
@@ -92,7 +92,7 @@ def test_mapper_train_forward_backward_equal_one_segment(hooks, n, update_stats)
         gpart = [torch.zeros(ng, device=DEV) for _ in range(2)]
         gpar = [_rand(30 + n, MG_SIZE, normal=True) for _ in range(2)]
         _ok(L.mcaq_mapper_train_backward(ctypes.byref(qs[0]), _p(c), n, _p(gbits), MIN_B, MAX_B, TEMP, _p(work[0]),
-                                         _p(gc[0]), _p(gpar[0]), _p(gpart[0]), acc, None, _stream()),
+                                         _p(gc[0]), _p(gpar[0]), _p(gpart[0]), acc, _stream()),
             "mcaq_mapper_train_backward")
         _ok(L.mcaq_mapper_train_backward_multi(ctypes.byref(qs[1]), _mseg(c, bits[1], work[1], gbits, gc[1], gpart[1]),
                                                1, MIN_B, MAX_B, TEMP, _stream()), "mcaq_mapper_train_backward_multi")

@@ -255,33 +255,37 @@ def test_direct_grad_accumulation_matches_autograd_return():
         _rel(res[True][k], res[False][k], 1e-5, floor=1e-12)
 
 
-def test_mapper_one_launch_equals_staged_launches():
-    """The train-mode mapper as ONE launch per direction (grid barriers
-    between the batch-statistics stages) gives the values of the per-stage
-    launches: bits, c gradient, parameter gradients and running stats."""
-    from mcaq_yolo_amd import core
-    W = load_weights()
-    g = torch.Generator().manual_seed(21)
-    res = {}
-    for one in (True, False):
-        old = core.MAPPER_ONE_LAUNCH
-        core.MAPPER_ONE_LAUNCH = one
-        try:
-            m = core.ComplexityToBitMappingNetwork().to(DEV)
-            m.load_state_dict({k[len("bit_mapper."):]: torch.from_numpy(np.asarray(v))
-                               for k, v in W.items() if k.startswith("bit_mapper.")})
-            m.train()
-            torch.manual_seed(21)
-            c = torch.rand(5, 37, 41).to(DEV).requires_grad_(True)     # 7585 tiles: 119 workgroups
-            bits = m(c, 2.0, return_continuous=True)
-            bits.backward(torch.randn(bits.shape, generator=g.manual_seed(22)).to(DEV))
-            torch.cuda.synchronize()
-            res[one] = ([bits.detach().clone(), c.grad.clone()] + [p.grad.clone() for p in m.parameters()] +
-                        [b.clone() for b in m.buffers()])
-        finally:
-            core.MAPPER_ONE_LAUNCH = old
-    for a, b in zip(res[True], res[False]):
-        assert torch.equal(a, b)
+def test_soft_mask_blobs_follow_the_module_not_its_addresses():
+    """train_step's soft-mask blob cache belongs to the parameters that were
+    packed, not to their addresses and versions: a second MCAQHooks whose
+    soft-mask parameters lie exactly where the first one's lay (here by
+    construction: both are views of one buffer, with equal version counters),
+    but hold other weights, quantizes with its own weights on its first
+    step, not with the first module's packed blobs."""
+    from test_concurrent_scales_gpu import _feats
+    buf = torch.empty(3 * 170, device=DEV)
+
+    def run(scale):
+        h = _hooks()
+        ps = [p for i in (4, 6, 9) for p in h.quantizers[str(i)].soft_mask.net.parameters()]
+        o = 0
+        with torch.no_grad():
+            for p in ps:
+                v = buf[o:o + p.numel()].view(p.shape)
+                v.copy_(p * scale)
+                p.data = v
+                o += p.numel()
+        assert o == buf.numel()
+        feats, _ = _feats(B=2)
+        outs, _ = h.forward_features(feats, temperature=1.0)
+        torch.cuda.synchronize()
+        return [y.detach().clone() for y in outs], [(p.data_ptr(), p._version) for p in ps]
+
+    (r1, k1), (r2, k2), (r3, k3), (r4, k4) = run(1.0), run(-0.5), run(1.0), run(-0.5)
+    assert k1 == k2 == k3 == k4                  # the same addresses and versions every time
+    assert not all(torch.equal(x, y) for x, y in zip(r1, r2))      # other weights, other outputs
+    for x, y in zip(r1 + r2, r3 + r4):
+        assert torch.equal(x, y)
 
 
 def test_pass1_sharing_equals_separate_passes():

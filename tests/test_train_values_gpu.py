@@ -114,7 +114,7 @@ def test_mapper_train_values(name, acc):
     work = torch.zeros(L.mcaq_mapper_work_floats(n), device=DEV)
     bits = torch.zeros(n, device=DEV)
     _ok(L.mcaq_mapper_train_forward(ctypes.byref(q), _p(c), n, tc.MIN_B, tc.MAX_B, T, 0.1, cfg["round"],
-                                    cfg["update_stats"], _p(bits), _p(work), None, _stream()),
+                                    cfg["update_stats"], _p(bits), _p(work), _stream()),
         "mcaq_mapper_train_forward")
     ng = L.mcaq_mapper_gpart_floats(n)
     assert ng // MG_SIZE == (n + tc.TR_TPB - 1) // tc.TR_TPB

@@ -6,9 +6,12 @@ about its registers (tools/kernel_regs.py)?
 
 Kernels are paired by demangled name; --rename rewrites OLD's names first (a
 kernel whose template arguments were renamed).  Addresses are stripped, so a
-kernel that only moved inside the code object compares equal.  Prints one
-line per kernel of NEW whose name contains PATTERN, then the kernels of OLD
-that have no partner."""
+kernel that only moved inside the code object compares equal.  Verdicts:
+`same` (the same text), `moved` (the same text but for the 32-bit literals of
+s_add_u32 / s_addc_u32: pc-relative addresses of constant data, which shift
+when other code of the object grows or shrinks) and `DIFF`.  Prints one line
+per kernel of NEW whose name contains PATTERN, then the kernels of OLD that
+have no partner."""
 import json
 import os
 import re
@@ -25,6 +28,11 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 def run(tool, *args, **kw):
     return subprocess.run([os.path.join(LLVM, tool)] + list(args), check=True, capture_output=True, text=True, **kw).stdout
+
+
+def unmoved(text):
+    """text with the literal operand of every s_add_u32 / s_addc_u32 masked"""
+    return re.sub(r"^(s_addc?_u32 .*, )(?:0x[0-9a-f]+|\d+)$", r"\1LIT", text, flags=re.M)
 
 
 def functions(so):
@@ -59,7 +67,9 @@ def compare(old_so, new_so, pattern, renames=()):
         if pattern not in mangled:
             continue
         o = old_by_name.pop(name, None)
-        recs.append({"kernel": name, "identical": o is not None and fo[o] == fn[mangled],
+        same = o is not None and fo[o] == fn[mangled]
+        moved = o is not None and not same and unmoved(fo[o]) == unmoved(fn[mangled])
+        recs.append({"kernel": name, "identical": same, "verdict": "same" if same else "moved" if moved else "DIFF",
                      "old": ro.get(o), "new": rn[mangled]})
     gone = sorted(v for v, k in old_by_name.items() if pattern in k)
     return recs, gone
@@ -78,11 +88,12 @@ if __name__ == "__main__":
         del a[i:i + 2]
     recs, gone = compare(a[0], a[1], a[2], renames)
     for r in recs:
-        print("same" if r["identical"] else "DIFF", r["kernel"],
+        print(r["verdict"], r["kernel"],
               "vgpr %s->%s" % ((r["old"] or {}).get("vgpr_count"), r["new"]["vgpr_count"]))
     for g in gone:
         print("gone", g)
-    print("%d kernels, %d identical, %d only in the old build" % (len(recs), sum(r["identical"] for r in recs), len(gone)))
+    print("%d kernels, %d identical, %d moved, %d only in the old build" % (
+        len(recs), sum(r["identical"] for r in recs), sum(r["verdict"] == "moved" for r in recs), len(gone)))
     if out:
         with open(out, "w") as f:
             json.dump({"kernels": recs, "only_in_old": gone}, f, indent=1)
