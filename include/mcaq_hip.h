@@ -642,7 +642,15 @@ int mcaq_stats_pack(const mcaq_stats_scale* scales, int nscales, const mcaq_pack
  * total_norm (1 float) receives the pre-clip norm, or NULL.  work:
  * mcaq_clip_adamw_work_floats(total elements) floats of device scratch.  Two
  * launches over 1,024-element chunks (per-chunk squared-norm partials, then
- * norm + update); capturable. */
+ * norm + update); capturable.
+ * Defined at the edges: with max_norm <= 0 neither the gradients nor
+ * *total_norm are written.  The squares are fp32 (torch's fp32
+ * clip_grad_norm_): a |g| above 1.8e19 makes the total inf.  Total inf:
+ * coef = 0, finite gradients become +-0 and their moments only decay, an inf
+ * gradient and its moments and parameter become NaN.  A NaN gradient makes,
+ * with clipping, the total and every gradient, moment and parameter of every
+ * segment NaN; without clipping only its own element.  Where the coefficient
+ * clamps to 1 the gradients keep their bits. */
 #define MCAQ_OPT_MAXSEG 64
 #define MCAQ_OPT_MAXGROUPS 4
 typedef struct {

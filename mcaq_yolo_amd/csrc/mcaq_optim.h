@@ -19,6 +19,20 @@
 // not bit for bit.  (Round 5 first ran both phases in ONE 1,024-thread
 // workgroup: 25 us in the graph; two launches over ~9 workgroups each take
 // less: the per-chunk work is one load round trip, not eight.)
+//
+// Defined at the edges (tests/optim_cases.py, test_optim_values_gpu.py pin
+// them against a float64 reference, per element):
+//  * max_norm <= 0: no clip - the gradients and *total_norm are not written.
+//  * The squares and their sums are fp32, as in torch's fp32 clip_grad_norm_:
+//    a |g| whose square overflows (|g| > 1.8e19) makes the total norm inf
+//    although the exact norm is finite.
+//  * Total inf (an inf gradient, or such an overflow): coef = max_norm / inf
+//    = 0, every finite gradient becomes +-0 and its moments only decay; an inf
+//    gradient times 0 is NaN, and so are that element's moments and parameter.
+//  * A NaN gradient with clipping: the total and the coefficient are NaN and
+//    with them every gradient, moment and parameter of every segment; without
+//    clipping only that element is NaN.
+//  * Where the coefficient clamps to 1 the gradients keep their bits.
 #pragma once
 
 namespace mcaq {

@@ -22,6 +22,10 @@ The two launches: per-chunk squared-norm partials, then the norm and the
 update of every chunk (csrc/mcaq_optim.h).  With clipping and up to 256
 chunks of 1,024 elements (ONE_LAUNCH) both run in ONE launch, the partials
 exchanged inside it (`mcaq_clip_adamw_fused`, bit-identical).
+Against a float64 reference, per element and at the kernels' edges:
+tests/optim_cases.py, tests/test_optim_values_gpu.py.  A group added with
+`add_param_group` after a step starts from zero moments at step 0 (as in
+torch); a parameter with no elements is left out of the step.
 """
 import ctypes
 import os
@@ -64,10 +68,20 @@ class ClipAdamW(torch.optim.Optimizer):
         device buffers and one step counter per parameter (torch.optim.AdamW
         keeps a step per parameter and skips parameters without a gradient),
         views of one device array (outside capture: the first step is a
-        warm-up)."""
+        warm-up).  Parameters that arrived later (add_param_group after a
+        step) get zero moments and step 0 in new buffers; the others' moments
+        and steps move over."""
         ps = [p for _, p in self._params()]
-        if self._flat is not None or not ps:
+        if not ps or (self._flat is not None and len(ps) == len(self._index) and
+                      all(id(p) in self._index for p in ps)):
             return
+        old = None
+        if self._flat is not None:
+            if ps[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("ClipAdamW: parameters were added; take one step outside graph capture first")
+            old = {p: dict(self.state[p]) for p in ps if id(p) in self._index}
+            self._retired.append((self._flat, self._steps_t))     # an earlier capture may still write into them
+            self._retire()
         dev = ps[0].device
         n = sum(p.numel() for p in ps)
         self._flat = (torch.zeros(n, device=dev), torch.zeros(n, device=dev))
@@ -81,6 +95,10 @@ class ClipAdamW(torch.optim.Optimizer):
             st["exp_avg_sq"] = self._flat[1][o:o + k].view_as(p)
             st["step"] = self._steps_t[i]
             o += k
+        for p, st in (old or {}).items():
+            self.state[p]["exp_avg"].copy_(st["exp_avg"])
+            self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
+            self.state[p]["step"].copy_(st["step"])
 
     def state_dict(self):
         """torch.optim.AdamW's layout.  Every parameter's step is its own CPU
@@ -144,7 +162,10 @@ class ClipAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        items = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"] if p.grad is not None]
+        # an empty parameter is no segment of the step (a segment has n >= 1):
+        # like one without a gradient it is left out and keeps its step
+        items = [(gi, p) for gi, g in enumerate(self.param_groups) for p in g["params"]
+                 if p.grad is not None and p.numel() > 0]
         if not items:
             return loss
         self._init_state()
