@@ -693,6 +693,43 @@ typedef struct {
 } mcaq_dp_seg;
 int mcaq_dp_unpack(const float* g, int world, int stride, const mcaq_dp_seg* segs, int nseg, hipStream_t stream);
 
+/* ---- percentile calibration (core/quantization.py:436-480) ----------------
+ * _calibrate_percentile: lo[c] / hi[c] = the q_lo / q_hi quantiles of channel
+ * c over its N = B*H*W values, as torch.quantile computes them (rank =
+ * fp32(q) * (N - 1), linear interpolation, SURVEY App. A rule 10) - EXACT
+ * over all N at every size (the reference samples 100,000 values when N is
+ * larger).  x: contiguous NCHW of `dtype` (MCAQ_DTYPE_*; fp16 / bf16 widen
+ * exactly: the quantile of x.float()); lo, hi: C floats.  A NaN in a channel
+ * makes its lo and hi NaN; -0 counts as +0.  Per tensor: describe the map as
+ * one channel (B = C = H = 1, W = numel).  Selection by a three-level radix
+ * histogram of an order-preserving key (csrc/mcaq_pct.h): one zeroing launch
+ * per call and six launches per scale, integer atomics only (results do not depend on arrival
+ * order), no host sync, capturable. */
+typedef struct {
+  const void* x; float* lo; float* hi;
+  int B, C, H, W, dtype;
+  float q_lo, q_hi;        /* in [0, 1]: percentile / 100 */
+} mcaq_percentile_scale;
+/* core/quantization.py:436-480: device scratch for C channels (for several
+ * scales in one call: C = the sum of their channels), 16-byte aligned. */
+size_t mcaq_percentile_workspace_bytes(int C);
+/* core/quantization.py:436-480.  hipErrorInvalidValue, before any launch,
+ * for N < 1, N >= 2^24 (fp32 rank arithmetic stops being exact; torch.quantile
+ * refuses above 16 M values), q outside [0, 1], a missing, short or
+ * misaligned workspace,
+ * an unknown dtype or more than MCAQ_MAX_SEGMENTS scales. */
+int mcaq_percentile(const mcaq_percentile_scale* scales, int nscales, void* workspace, size_t workspace_bytes,
+                    hipStream_t stream);
+/* The bit map's gradient of the training quantizer in the REFERENCE's
+ * summation order (core/quantization.py:699-727 under autograd; used by the
+ * percentile mode, core/quantization.py:436-480): per pixel sum_c(g' Q_hi) -
+ * sum_c(g' Q_lo), each sum in ATen's CPU outer-reduction order, then each
+ * tile's pixels row by row - grad_bits equal to the reference's bit for bit,
+ * where mcaq_qat_backward sums the same terms in its own order.  Reads x, g,
+ * bits, m (or NULL), xmin, xmax of mcaq_qat_scale; writes gb (B, ht, wt);
+ * work: B*H*W floats of scratch.  1..3 scales, two launches each. */
+int mcaq_qat_bits_gradient(const mcaq_qat_scale* scales, int nscales, hipStream_t stream);
+
 int mcaq_abi_version(void);
 
 #ifdef __cplusplus

@@ -148,6 +148,12 @@ class DpSeg(ctypes.Structure):
     _fields_ = [("out", P), ("off", I), ("n", I), ("mode", I)]
 
 
+class PercentileScale(ctypes.Structure):
+    """mcaq_percentile_scale (core/quantization.py:436-480)."""
+    _fields_ = [("x", P), ("lo", P), ("hi", P), ("B", I), ("C", I), ("H", I), ("W", I), ("dtype", I),
+                ("q_lo", Fl), ("q_hi", Fl)]
+
+
 # morph stage flags (mcaq_morph.h)
 F_PHI, F_CMLP, F_MAPPER, F_SOFTMASK = 1, 2, 4, 8
 F_CONT, F_HAS_T, F_NORM_C, F_MAP_LINEAR = 16, 32, 64, 128
@@ -175,7 +181,8 @@ EXPORTS = ("mcaq_abi_version", "mcaq_launch_spatial_quantization", "mcaq_stats",
            "mcaq_stats_pack", "mcaq_morph_ema", "mcaq_mapper_train_backward_multi_ride", "mcaq_dp_unpack",
            "mcaq_mapper_sync_bytes", "mcaq_mapper_fused_max_wg", "mcaq_mapper_train_forward_fused",
            "mcaq_mapper_train_backward_fused",
-           "mcaq_qat_forward_tile_losses", "mcaq_tile_losses_forward", "mcaq_qat_smask_backward_tile_losses")
+           "mcaq_qat_forward_tile_losses", "mcaq_tile_losses_forward", "mcaq_qat_smask_backward_tile_losses",
+           "mcaq_percentile", "mcaq_percentile_workspace_bytes", "mcaq_qat_bits_gradient")
 
 _LIB = None
 
@@ -190,7 +197,8 @@ def _declare(lib):
     lib.mcaq_launch_spatial_quantization.argtypes = [P, P, P, P, P, P] + [I] * 8 + [P]
     for n, st in (("mcaq_stats", StatsScale), ("mcaq_finalize", FinalizeScale),
                   ("mcaq_morph", MorphScale), ("mcaq_quant", QuantScale),
-                  ("mcaq_qat_forward", QatScale), ("mcaq_qat_backward", QatScale)):
+                  ("mcaq_qat_forward", QatScale), ("mcaq_qat_backward", QatScale),
+                  ("mcaq_qat_bits_gradient", QatScale)):
         f = getattr(lib, n)
         f.restype = I
         f.argtypes = [ctypes.POINTER(st), I, P]
@@ -318,6 +326,10 @@ def _declare(lib):
     lib.mcaq_clip_adamw_fused.argtypes = [ctypes.POINTER(AdamwSeg), I, P, I, P, Fl, P, P, ctypes.c_size_t, P]
     lib.mcaq_dp_unpack.restype = I
     lib.mcaq_dp_unpack.argtypes = [P, I, I, ctypes.POINTER(DpSeg), I, P]
+    lib.mcaq_percentile_workspace_bytes.restype = ctypes.c_size_t
+    lib.mcaq_percentile_workspace_bytes.argtypes = [I]
+    lib.mcaq_percentile.restype = I
+    lib.mcaq_percentile.argtypes = [ctypes.POINTER(PercentileScale), I, P, ctypes.c_size_t, P]
     lib.mcaq_smask_train_backward.restype = I
     lib.mcaq_smask_train_backward.argtypes = [ctypes.POINTER(SmaskParams), P, P, P, I, I, I, I, I, P, I, P, P, P]
     return lib

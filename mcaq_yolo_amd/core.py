@@ -397,6 +397,49 @@ def _channel_minmax(x, absmean=None, partials=None):
     return xmin, xmax
 
 
+CALIBRATION_MODES = ("minmax", "percentile")
+
+
+def channel_percentiles(x, q_lo, q_hi, per_channel=True, out=None, workspace=None):
+    """_calibrate_percentile's two quantiles (quantization.py:436-480) of a CUDA
+    map on the HIP kernels (mcaq_percentile, csrc/mcaq_pct.h): the q_lo / q_hi
+    quantiles (fractions in [0, 1]) of every channel over (batch, H, W), or of
+    the whole tensor (per_channel=False: one entry), exactly as
+    torch.quantile(x.float() rows, q) computes them over ALL values.  x: fp32,
+    or fp16 / bf16 read as it is.  No host sync; capturable.  out: (lo, hi)
+    fp32 buffers to fill, workspace: a uint8 buffer of
+    mcaq_percentile_workspace_bytes(entries) bytes (a caller that replays a
+    captured step keeps both alive); default: fresh tensors."""
+    _need_cuda(x, "x")
+    xf = x.detach()
+    if xf.dtype not in _ABI_DTYPES:
+        xf = xf.float()
+    xf = xf.contiguous()
+    L = abi.lib()
+    s = abi.PercentileScale()
+    if per_channel:
+        if xf.dim() < 2:
+            raise ValueError("per-channel percentiles need a (B, C, ...) map")
+        s.B, s.C, s.H = xf.shape[0], xf.shape[1], 1
+        s.W = xf.numel() // max(1, s.B * s.C)
+    else:
+        s.B, s.C, s.H, s.W = 1, 1, 1, xf.numel()
+    n = s.C
+    lo, hi = out if out is not None else (torch.empty(n, device=xf.device), torch.empty(n, device=xf.device))
+    need = L.mcaq_percentile_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=xf.device)
+    for t in (lo, hi):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError("out: two contiguous fp32 CUDA tensors of %d entries" % n)
+    s.x, s.lo, s.hi = _p(xf), _p(lo), _p(hi)
+    s.dtype = _ABI_DTYPES[xf.dtype]
+    s.q_lo, s.q_hi = float(q_lo), float(q_hi)
+    abi.check(L.mcaq_percentile(ctypes.byref(s), 1, _p(workspace), workspace.numel() * workspace.element_size(),
+                                _stream()), "mcaq_percentile")
+    return lo, hi
+
+
 # ---------------------------------------------------------------------------
 # morphology.py
 # ---------------------------------------------------------------------------
@@ -1496,6 +1539,39 @@ class _QATQuantFn(torch.autograd.Function):
         return gx, gb, gm, None, None
 
 
+def qat_bits_gradient_reference_order(g, x, bits, m, xmin, xmax):
+    """grad_bits of the training quantizer summed as the reference's autograd
+    graph sums it (quantization.py:699-727; mcaq_qat_bits_gradient,
+    csrc/mcaq_pct.h): per pixel the channel sums of g' Q_hi and of g' Q_lo
+    in ATen's CPU outer-reduction order, then each tile's pixels row by row.
+    Equal to the reference's gradient bit for bit (qat_quantize_backward
+    sums the same terms in its kernel's order)."""
+    B, C, H, W = x.shape
+    gb = torch.empty(bits.shape, device=x.device)
+    work = torch.empty(B * H * W, device=x.device)
+    q = _qat_struct(x, bits, m, xmin, xmax)
+    q.g, q.gb, q.work = _p(g), _p(gb), _p(work)
+    abi.check(abi.lib().mcaq_qat_bits_gradient(ctypes.byref(q), 1, _stream()), "mcaq_qat_bits_gradient")
+    return gb
+
+
+class _QATQuantRefOrderFn(_QATQuantFn):
+    """_QATQuantFn whose gradient to the bit map is summed in the reference's
+    order (percentile mode: the module then equals the reference's train step
+    bit for bit, y, grad x and grad bits)."""
+
+    @staticmethod
+    def backward(ctx, g):
+        xf, bits, mf, xmin, xmax = ctx.saved_tensors
+        gf = _f32c(g)
+        gx, _, gm = qat_quantize_backward(gf, xf, bits, mf, xmin, xmax, want_gm=ctx.needs_input_grad[2],
+                                          want_gb=False)
+        gb = qat_bits_gradient_reference_order(gf, xf, bits, mf, xmin, xmax) if ctx.needs_input_grad[1] else None
+        if gm is not None:
+            gm = gm.view(mf.shape)
+        return gx, gb, gm, None, None
+
+
 class SpatialAdaptiveQuantization(nn.Module):
     """quantization.py:242-754, inference: per-channel (batch, H, W) min/max (or
     frozen calibration stats) -> per-tile 2..8-bit quant/dequant x m(p).
@@ -1510,19 +1586,42 @@ class SpatialAdaptiveQuantization(nn.Module):
     map at inference with the batch's own statistics (per channel or per
     tensor); frozen / EMA statistics are fp32 buffers, which promote the
     reference's arithmetic to fp32, and keep the fp32 path.  A plain
-    attribute, not part of the state_dict."""
+    attribute, not part of the state_dict.
+
+    calibration_mode: "minmax" (default) or "percentile"
+    (_calibrate_percentile, quantization.py:436-480): the range of a channel
+    (or of the tensor) is its percentile_min / percentile_max percentiles
+    (0.01 / 99.99, the reference's defaults; plain attributes, not in the
+    state_dict) of the CURRENT batch, by torch.quantile's rule.  As in the
+    reference, frozen and EMA statistics are not read in this mode
+    (update_running_stats still maintains them in training / calibration),
+    and no gradient flows through the quantiles.  One deviation: the
+    reference estimates the quantiles from a random 100,000-value sample
+    when a channel has more values; this package always computes the EXACT
+    quantile over all values - for up to 100,000 values that is the
+    reference's result bit for bit, above that the quantity it estimates.
+    fp16 / bf16 maps (where the reference's torch.quantile raises) are
+    quantized in fp32 on the exactly widened values; half_arithmetic=
+    "reference" and a process group are refused in this mode.  "entropy" and
+    "mse" are refused."""
 
     def __init__(self, calibration_mode: str = "minmax", smooth_transitions: bool = True,
                  per_channel: bool = True, learned_rounding: bool = False, momentum: float = 0.99,
                  half_arithmetic: str = "fp32"):
         super().__init__()
         self.half_arithmetic = _check_half_arithmetic(half_arithmetic)
-        if calibration_mode != "minmax":
-            raise NotImplementedError("calibration_mode=%r: the hooks use 'minmax' "
-                                      "(models/mcaq_yolo.py:466-470)" % calibration_mode)
+        if calibration_mode not in CALIBRATION_MODES:
+            raise NotImplementedError("calibration_mode=%r: 'minmax' (the hooks' default, models/mcaq_yolo.py:"
+                                      "466-470) and 'percentile' are on this path" % (calibration_mode,))
+        if calibration_mode == "percentile" and self.half_arithmetic == "reference":
+            raise NotImplementedError("calibration_mode='percentile' with half_arithmetic='reference': the "
+                                      "reference cannot run this mode on fp16 / bf16 maps (torch.quantile: "
+                                      "'input tensor must be either float or double')")
         if learned_rounding:
             raise NotImplementedError("learned_rounding is never enabled by the reference hooks")
         self.calibration_mode = calibration_mode
+        # quantization.py:291-292 (not constructor arguments there either)
+        self.percentile_min, self.percentile_max = 0.01, 99.99
         self.smooth_transitions = smooth_transitions
         self.per_channel = per_channel
         self.momentum = momentum
@@ -1567,6 +1666,45 @@ class SpatialAdaptiveQuantization(nn.Module):
             xmin = xmin.amin().expand(x.shape[1]).contiguous()
             xmax = xmax.amax().expand(x.shape[1]).contiguous()
         return xmin, xmax
+
+    def _percentile(self):
+        """True in percentile mode; refuses what that mode does not cover."""
+        if self.calibration_mode != "percentile":
+            return False
+        if self.process_group is not None:
+            raise NotImplementedError("calibration_mode='percentile' with a process group: a global-batch "
+                                      "quantile needs the level histograms all-reduced (DESIGN.md s.7)")
+        if _check_half_arithmetic(self.half_arithmetic) == "reference":
+            raise NotImplementedError("calibration_mode='percentile' with half_arithmetic='reference' "
+                                      "(torch.quantile raises on fp16 / bf16 inputs)")
+        return True
+
+    def batch_percentiles(self, x, out=None, workspace=None):
+        """_calibrate_percentile (quantization.py:436-480): the percentile_min /
+        percentile_max percentiles of every channel over (batch, H, W) - or of
+        the tensor (per_channel=False) - expanded to C entries: (lo, hi).
+        torch.quantile's rule over ALL values (the reference samples 100,000
+        of them when there are more).  HIP tensors: the native launch
+        (channel_percentiles; fp16 / bf16 read as they are); CPU tensors:
+        torch.quantile over the full rows of x.float().  out / workspace
+        (HIP only): see channel_percentiles."""
+        if self.process_group is not None:
+            raise NotImplementedError("batch percentiles with a process group: a global-batch quantile needs "
+                                      "the level histograms all-reduced (DESIGN.md s.7)")
+        C = x.shape[1]
+        q_lo, q_hi = self.percentile_min / 100, self.percentile_max / 100
+        if x.is_cuda:
+            lo, hi = channel_percentiles(x, q_lo, q_hi, self.per_channel, out, workspace)
+        else:
+            xf = x.detach().float()
+            if self.per_channel:
+                rows = xf.transpose(0, 1).flatten(1)
+                lo, hi = torch.quantile(rows, q_lo, dim=1), torch.quantile(rows, q_hi, dim=1)
+            else:
+                lo, hi = torch.quantile(xf.flatten(), q_lo).reshape(1), torch.quantile(xf.flatten(), q_hi).reshape(1)
+        if lo.numel() == 1 and C != 1:
+            lo, hi = lo.expand(C), hi.expand(C)
+        return lo.contiguous(), hi.contiguous()
 
     def _global_minmax(self, xmin, xmax):
         """Batch-sharded data parallelism: min/max over the global batch with one
@@ -1678,11 +1816,16 @@ class SpatialAdaptiveQuantization(nn.Module):
             if want_m and hit is None:
                 _run_stats(xf, absmean=absmean)
         else:
-            copies = self.update_running_stats(xf, absmean, want_copies=self.training)
+            copies = self.update_running_stats(xf, absmean, want_copies=self.training and
+                                               self.calibration_mode == "minmax")
         # _calibrate_minmax (quantization.py:409-434): running stats in train
         # mode or when frozen, else this batch's min/max (copies: the running
         # buffers are updated in place by later steps)
-        if copies is not None:
+        if self._percentile():
+            # quantization.py:436-480: this batch's percentiles, whatever the
+            # running statistics hold; no gradient through them
+            xmin, xmax = self.batch_percentiles(xf)
+        elif copies is not None:
             xmin, xmax = copies
         elif self.running_min is not None and (self.training or frozen):
             xmin = self._stats_c(self.running_min, C).clone()
@@ -1690,7 +1833,8 @@ class SpatialAdaptiveQuantization(nn.Module):
         else:
             xmin, xmax = self.batch_minmax(xf)
         m = self.soft_mask(bit_map, x, absmean=absmean) if want_m else None
-        return _QATQuantFn.apply(x, bit_map, m, xmin, xmax)
+        fn = _QATQuantRefOrderFn if self.calibration_mode == "percentile" else _QATQuantFn
+        return fn.apply(x, bit_map, m, xmin, xmax)
 
     def _minmax_for_quant(self, x):
         """_calibrate_minmax (quantization.py:409-434): running statistics in
@@ -1736,10 +1880,13 @@ class SpatialAdaptiveQuantization(nn.Module):
             return self._forward_reference_half(x, bit_map)
         if training:
             self.update_running_stats(x)
-        xmin, xmax = self._minmax_for_quant(x)
+        xmin, xmax = self.batch_percentiles(x) if self._percentile() else self._minmax_for_quant(x)
         xmin = xmin.reshape(-1).float().expand(C) if xmin.numel() == 1 else xmin.reshape(-1).float()
         xmax = xmax.reshape(-1).float().expand(C) if xmax.numel() == 1 else xmax.reshape(-1).float()
-        if training:
+        if training and self.calibration_mode == "percentile":
+            # the reference's own autograd graph: its gradients bit for bit
+            xq = fallback.fractional_quant_graph(x.float(), bit_map.float(), xmin.contiguous(), xmax.contiguous())
+        elif training:
             xq = fallback.FractionalQuant.apply(x.float(), bit_map, xmin.contiguous(), xmax.contiguous())
         else:
             with torch.no_grad():
@@ -1751,6 +1898,7 @@ class SpatialAdaptiveQuantization(nn.Module):
     def forward(self, x: torch.Tensor, bit_map: torch.Tensor, training: Optional[bool] = None) -> torch.Tensor:
         if training is None:
             training = self.training
+        self._percentile()      # refuses the combinations percentile mode does not cover
         if not x.is_cuda:
             return self._forward_torch(x, bit_map, training)
         if training:
@@ -1775,7 +1923,14 @@ class SpatialAdaptiveQuantization(nn.Module):
         want_m = self.smooth_transitions and self.soft_mask is not None
         absmean = torch.empty(B, H, W, device=xf.device) if want_m else None
         frozen = bool(self.stats_frozen) and self.running_min is not None
-        if frozen:
+        pct = self._percentile()
+        if pct:
+            # the percentiles of x as it came (a half map is read natively);
+            # frozen / EMA statistics are not read in this mode
+            xmin, xmax = self.batch_percentiles(x if x.dtype in _ABI_DTYPES else xf)
+            if want_m:
+                _run_stats(xf, absmean=absmean)
+        elif frozen:
             xmin = self.running_min.reshape(-1).float().expand(C).contiguous() \
                 if self.running_min.numel() == 1 else self.running_min.reshape(-1).float().contiguous()
             xmax = self.running_max.reshape(-1).float().expand(C).contiguous() \
@@ -1791,7 +1946,7 @@ class SpatialAdaptiveQuantization(nn.Module):
         q.x, q.y, q.bits, q.mt, q.xmin, q.xmax = _p(xf), _p(y), _p(bits), _p(mt), _p(xmin), _p(xmax)
         q.B, q.C, q.H, q.W, q.ht, q.wt = B, C, H, W, ht, wt
         q.bits_lo, q.nbits = 2, 7
-        q.stats_cover_x = 0 if frozen else 1
+        q.stats_cover_x = 0 if (frozen or pct) else 1
         q.dtype = _ABI_DTYPES[xf.dtype]
         q.arith = abi.ARITH_REFERENCE if ref else abi.ARITH_FP32
         abi.check(abi.lib().mcaq_quant(ctypes.byref(q), 1, _stream()), "mcaq_quant")

@@ -1309,6 +1309,7 @@ int mcaq_morph_pass(const mcaq_morph_scale* scales, int nscales, const mcaq_fina
 #include "mcaq_train.h"
 #include "mcaq_optim.h"
 #include "mcaq_dp.h"
+#include "mcaq_pct.h"
 
 // C++-linkage drop-in for the reference's declaration (include/mcaq_hip.h):
 // same name, argument list and void return as MCAQPlugin.cpp:15-23.  An

@@ -542,6 +542,50 @@ class FractionalQuant(torch.autograd.Function):
         return gx, gb, None, None, None
 
 
+class _WidthSTE(torch.autograd.Function):
+    """One width's quantize / dequantize with the straight-through backward
+    (StraightThroughEstimator, quantization.py:69-118)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, zp, qmin, qmax):
+        return (torch.clamp(torch.round(x / scale + zp), qmin, qmax) - zp) * scale
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.clone(), None, None, None, None
+
+
+def fractional_quant_graph(x, bits, xmin, xmax, hi_bits=8):
+    """The fractional-bit training quantizer as the reference's own autograd
+    graph (quantization.py:699-727): width by width over the floors present
+    in the bit map, x_q += sel (1 - f) Q_b(x) + sel f Q_b+1(x) with the
+    nearest-upsampled tile selection sel and fraction f.  Same values as
+    FractionalQuant; the gradients - the bit map's among them, which autograd
+    sums path by path and width by width in fp32 - are the reference's bit
+    for bit on CPU tensors.  xmin / xmax: C entries, no gradient."""
+    B, C, H, W = x.shape
+    xmin = xmin.detach().reshape(1, C, 1, 1).float()
+    xmax = xmax.detach().reshape(1, C, 1, 1).float()
+    span = torch.clamp(xmax - xmin, min=1e-8)
+
+    def q(width):
+        qmin, qmax = -(2 ** (width - 1)), 2 ** (width - 1) - 1
+        scale = span / (qmax - qmin)
+        zp = torch.clamp(qmin - xmin / scale, qmin, qmax)
+        return _WidthSTE.apply(x, scale, zp, qmin, qmax)
+
+    b_floor = torch.floor(bits)
+    frac_up = F.interpolate((bits - b_floor).unsqueeze(1), size=(H, W), mode="nearest")
+    out = torch.zeros_like(x)
+    for bf in torch.unique(b_floor.detach()):
+        w = int(bf.item())
+        sel_up = F.interpolate((b_floor == bf).float().unsqueeze(1), size=(H, W), mode="nearest")
+        q_lo = q(w)
+        q_hi = q(w + 1) if w + 1 <= hi_bits else q_lo
+        out = out + sel_up * ((1.0 - frac_up) * q_lo + frac_up * q_hi)
+    return out
+
+
 def ema_update(running_min, running_max, xmin, xmax, momentum):
     """update_running_stats (quantization.py:340-347): first batch takes the
     batch statistics, later ones r <- momentum r + (1 - momentum) new."""

@@ -59,8 +59,14 @@ def smoothness_of(bit_map):
 
 class MCAQHooks(nn.Module):
     def __init__(self, grid_size=8, min_bits=2, max_bits=8, bit_mapping="mlp", normalize_complexity=False,
-                 device="cuda", indices=DEFAULT_INDICES, half_arithmetic="fp32"):
-        """half_arithmetic: "fp32" (default) quantizes an fp16 / bf16 map in
+                 device="cuda", indices=DEFAULT_INDICES, half_arithmetic="fp32", calibration_mode="minmax"):
+        """calibration_mode: "minmax" (the reference hooks', models/mcaq_yolo.py:
+        466-470) or "percentile" - every quantizer's range is its batch's 0.01 /
+        99.99 percentiles (core.SpatialAdaptiveQuantization: exact over all
+        values, where the reference samples 100,000; not with a process group,
+        not with half_arithmetic="reference").  Not part of the state_dict.
+
+        half_arithmetic: "fp32" (default) quantizes an fp16 / bf16 map in
         fp32 on the exactly widened values; "reference" reproduces the
         reference's own arithmetic under autocast, every elementwise result
         rounded to the map's dtype (core.SpatialAdaptiveQuantization).  The
@@ -79,7 +85,7 @@ class MCAQHooks(nn.Module):
         self.quantizers = nn.ModuleDict()
         self.backbone_out_indices = list(indices)
         for idx in self.backbone_out_indices:
-            self.quantizers[str(idx)] = SpatialAdaptiveQuantization(calibration_mode="minmax",
+            self.quantizers[str(idx)] = SpatialAdaptiveQuantization(calibration_mode=calibration_mode,
                                                                     smooth_transitions=True, per_channel=True,
                                                                     half_arithmetic=half_arithmetic)
         self._mcaq_state = {"active": False}
@@ -210,6 +216,21 @@ class MCAQHooks(nn.Module):
             self._plans[key] = plan
         return plan
 
+    @staticmethod
+    def _percentile_buffers(plan, quantizer, x):
+        """(lo, hi) of x by the quantizer's percentile rule, in the plan's own
+        persistent buffers (one entry per channel, or one for a per-tensor
+        quantizer)."""
+        n = x.shape[1] if quantizer.per_channel else 1
+        p = plan.__dict__.get("_pct")
+        if p is None or p["lo"].numel() != n:
+            nbytes = plan.lib.mcaq_percentile_workspace_bytes(n)
+            p = {"lo": torch.empty(n, device=x.device), "hi": torch.empty(n, device=x.device),
+                 "ws": torch.empty(nbytes, dtype=torch.uint8, device=x.device)}
+            plan._pct = p
+        return core.channel_percentiles(x, quantizer.percentile_min / 100, quantizer.percentile_max / 100,
+                                        quantizer.per_channel, out=(p["lo"], p["hi"]), workspace=p["ws"])
+
     def _run_scale_modules(self, layer_idx, feat, state):
         """models/mcaq_yolo.py:409-455 module by module: train mode (QAT,
         BASELINE config 5: analyzer with autograd into complexity_mlp,
@@ -311,7 +332,16 @@ class MCAQHooks(nn.Module):
         for k in ("y", "complexity", "bits"):      # fresh outputs: the caller keeps them
             b[k] = torch.empty_like(b[k])
         minmax = None
-        if quantizer._frozen() and quantizer.running_min is not None:
+        if quantize and quantizer._percentile():
+            # percentile calibration: this batch's quantiles, computed on the
+            # current stream into buffers that live with the plan slot (a
+            # captured step replays them; the plan's descriptors stay valid),
+            # go where frozen statistics go; frozen / EMA statistics are not read
+            if self.process_group is not None:
+                raise NotImplementedError("calibration_mode='percentile' on a batch-sharded map: a global-batch "
+                                          "quantile needs the level histograms all-reduced (DESIGN.md s.7)")
+            minmax = [self._percentile_buffers(plan, quantizer, x)]
+        elif quantizer._frozen() and quantizer.running_min is not None:
             minmax = [(quantizer.running_min.reshape(-1), quantizer.running_max.reshape(-1))]
         an = self.complexity_analyzer
         sm = quantizer.soft_mask.blob() if (quantizer.smooth_transitions and quantizer.soft_mask is not None) \
@@ -352,6 +382,8 @@ class MCAQHooks(nn.Module):
     def _concurrent_ok(self, feats):
         if not (CONCURRENT_TRAIN_SCALES and self.training and core.FUSED_TRAIN and len(feats) > 1):
             return False
+        if any(q.calibration_mode != "minmax" for q in self.quantizers.values()):
+            return False            # percentile calibration: one stream, scale after scale
         if not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 4 for f in feats):
             return False
         if len({f.device for f in feats}) != 1:

@@ -1003,6 +1003,10 @@ def multi_ok(hooks, feats):
         return False
     if not hooks.bit_mapper.training or not all(q.training for q in hooks.quantizers.values()):
         return False
+    # the fused step quantizes with the EMA statistics; percentile calibration
+    # (this batch's quantiles) takes the per-scale modules
+    if any(q.calibration_mode != "minmax" for q in hooks.quantizers.values()):
+        return False
     if not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 4 for f in feats):
         return False
     if len({f.device for f in feats}) != 1 or len(feats) > abi.MCAQ_TRAIN_MAXSEG:

@@ -317,13 +317,14 @@ class MCAQYOLO(MCAQHooks):
 
     def __init__(self, model_name="yolov8n", pretrained=False, min_bits=2, max_bits=8, target_bits=4.0,
                  device="cuda", num_classes=80, grid_size=8, bit_mapping="mlp", normalize_complexity=False,
-                 weights=None):
+                 weights=None, calibration_mode="minmax"):
         if pretrained and weights is None:
             raise RuntimeError("pretrained ultralytics weights are not available offline; pass weights=<file>")
         model = DetectionModel(model_name, nc=num_classes)
         indices = find_backbone_out_indices(model.model)
         super().__init__(grid_size=grid_size, min_bits=min_bits, max_bits=max_bits, bit_mapping=bit_mapping,
-                         normalize_complexity=normalize_complexity, device=device, indices=indices)
+                         normalize_complexity=normalize_complexity, device=device, indices=indices,
+                         calibration_mode=calibration_mode)
         self.model = model
         self.num_classes = num_classes
         self.target_bits = target_bits
